@@ -3,7 +3,9 @@
 config C2), achieved fraction of the HBM roofline for the dominant kernel (with the roof that actually binds
 it, VALU issue, measured beside it), and the CPU oracle timed in the same run.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) so that two builds can be compared output for output.
 
 A "step" = one pass of the hot path (PostProcessor::Apply for both eyes of every pair) over one batch of
 `--pairs` synthetic stereo pairs per GPU that are already resident in HBM.  Batches shard embarrassingly
@@ -179,6 +181,16 @@ class GpuShard:
 
     def step(self):
         self.pp.apply_batch(self.texs, self.outs, first_eye=self.A.EYE_LEFT, alternate_eyes=True, shared=self.shared)
+
+    def output_sample(self, index):
+        """Host copy (float32) of the given flat element indices (int64 numpy array) of the output batch, gathered on the device."""
+        flat = self.outs.view(-1)
+        if index is None:
+            return flat.float().cpu().numpy().reshape(self.outs.shape)
+        return flat[torch.from_numpy(index).to(self.dev)].float().cpu().numpy()
+
+    def output_numel(self):
+        return self.outs.numel()
 
     def fetch(self, indices):
         """(input, output) host copies of the given images of the batch the timed call just processed."""
@@ -960,6 +972,30 @@ def frame_leg(args, shard, frames=520):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: all files of one run together, .npy headers included stay below 64 MB
+DUMP_SEED = 0x0D0C5EED
+
+
+def dump_outputs(out_dir, shards, n_gpus):
+    """--dump-outputs DIR: what the timed path computed in its LAST timed step (the output batch of every local shard, before any later leg
+    writes it), as float32 .npy files.  A shard whose output fits its share of DUMP_BUDGET_BYTES is written whole (shard<s>_outputs.npy, the
+    batch's own shape); a larger one as a fixed, seeded sample of its flat elements: shard<s>_outputs_sample.npy (values) beside
+    shard<s>_outputs_sample_index.npy (sorted flat indices, float64).  Inputs are seeded, so equal arguments give equal files on a correct build."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, n_gpus)
+    for s in shards:
+        s.sync()
+        numel = s.output_numel()
+        name = os.path.join(out_dir, "shard%d_outputs" % s.shard_index)
+        if numel * 4 <= share:
+            np.save(name + ".npy", np.ascontiguousarray(s.output_sample(None), dtype=np.float32))
+            continue
+        rng = np.random.default_rng(DUMP_SEED + s.shard_index)
+        index = np.unique(rng.integers(0, numel, size=share // 12, dtype=np.int64))   # 4 bytes of value + 8 of index per element
+        np.save(name + "_sample.npy", np.ascontiguousarray(s.output_sample(index), dtype=np.float32))
+        np.save(name + "_sample_index.npy", index.astype(np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -980,7 +1016,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="skip the un-timed extra legs (content_random, content_natural, frame)")
     ap.add_argument("--content", default="structured", choices=["structured", "random"],
                     help="synthetic eye content: structured (gradients+edges+noise, default) or uniform random")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/*.npy (float32, below 64 MB in all: a seeded sample of larger outputs); "
+                         "bench_outputs/ is ignored by git")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def plan(args, env):
@@ -1054,6 +1096,8 @@ def main(argv=None):
     dt = max_over_ranks(dt_local, world)
     dev_ms_local0 = dev_ms[0] if dev_ms else None   # shard 0 of THIS process: HIP events around exactly the timed steps
     dev_ms = gather_over_ranks(dev_ms, world)   # one entry per GPU of the job, whatever the launcher
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shards, n_gpus)   # before any later leg writes the output batches
     # every shard checks image 0 of its own timed batch against the oracle (collective: every rank contributes its records)
     per_shard = None if args.no_verify else gather_over_ranks([shard_parity(args, s) for s in shards], world)
 

@@ -54,6 +54,14 @@ class MockShard:
             out.append((src, got))
         return out
 
+    # --dump-outputs: the "output batch" of a mock shard is image 0 of fetch()
+    def output_numel(self):
+        return self.fetch([0])[0][1].size
+
+    def output_sample(self, index):
+        out = self.fetch([0])[0][1].astype(np.float32)
+        return out if index is None else out.reshape(-1)[index]
+
     def close(self):
         pass
 

@@ -169,3 +169,54 @@ def test_torchrun_fails_and_names_a_corrupted_shard():
     ps = d["parity_check"]["per_shard"]
     assert len(ps) == n and [r["shard"] for r in ps if not r["ok"]] == [k]
     assert "shard %d (device %d)" % (k, k) in err
+
+
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_the_last_timed_step_reproducibly(tmp_path):
+    """`bench.py --dump-outputs DIR`: one float32 .npy per shard, below 64 MB in all, the same files from two runs with the same arguments;
+    --steps still sets the number of timed steps and the line still carries ms_per_step."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+        _check_line(d, 2, 4, 1, 64)
+        files = sorted(os.listdir(out))
+        assert files == ["shard0_outputs.npy", "shard1_outputs.npy"], files
+        assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        runs.append({f: np.load(out / f) for f in files})
+    for f, a in runs[0].items():
+        assert a.dtype == np.float32 and a.ndim == 3 and a.shape[-1] == 4
+        assert np.array_equal(a, runs[1][f])
+    assert not np.array_equal(runs[0]["shard0_outputs.npy"], runs[0]["shard1_outputs.npy"])   # each shard its own seeds
+
+
+def test_dump_outputs_samples_a_large_batch_within_budget(tmp_path):
+    """an output batch larger than the budget is dumped as a fixed, seeded sample: values and their flat indices"""
+    import numpy as np
+    import bench
+
+    class Big:
+        shard_index = 3
+
+        def __init__(self):
+            self.full = (np.arange(40 << 20, dtype=np.int64) % 251).astype(np.float32)
+
+        def sync(self):
+            pass
+
+        def output_numel(self):
+            return self.full.size
+
+        def output_sample(self, index):
+            return self.full if index is None else self.full[index]
+
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), [Big()], 1)
+    files = sorted(os.listdir(tmp_path / "0"))
+    assert files == ["shard3_outputs_sample.npy", "shard3_outputs_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in files) < 64 << 20
+    v, i = np.load(tmp_path / "0" / files[0]), np.load(tmp_path / "0" / files[1])
+    assert v.dtype == np.float32 and i.dtype == np.float64 and v.shape == i.shape and v.size > 1 << 20
+    assert np.array_equal(v, (i.astype(np.int64) % 251).astype(np.float32))
+    assert np.array_equal(i, np.load(tmp_path / "1" / files[1])) and np.array_equal(v, np.load(tmp_path / "1" / files[0]))

@@ -51,9 +51,9 @@ def test_unreadable_config_keeps_struct_defaults():
     assert cfg.fsr_enabled == 0 and cfg.sharpness == 0.75 and cfg.render_scale == 1.0   # Config.h:11-15
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/openvr_mod.cfg"), reason="reference tree not present")
 def test_reference_shipped_file():
-    rc, cfg = A.config_from_json(open("/root/reference/src/openvr_mod.cfg").read())
+    # tests/golden/openvr_mod.cfg: the configuration file the reference ships, byte for byte
+    rc, cfg = A.config_from_json(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "openvr_mod.cfg")).read())
     assert rc == 0 and cfg.fsr_enabled == 1 and cfg.use_nis == 0
     assert abs(cfg.render_scale - 0.77) < 1e-7 and abs(cfg.sharpness - 0.9) < 1e-7 and cfg.radius == 0.5 and cfg.debug_mode == 0
 

@@ -4,7 +4,7 @@ Three implementations are checked against the committed outputs of the reference
 (tests/golden/ref_consts.json, produced by tests/golden/make_golden.py from oracle/_ref):
   * the product library's host code (ovrfsr_easu_con / ovrfsr_rcas_con / ovrfsr_nis_* via the C ABI),
   * the oracle's C restatement,
-  * and, where oracle/_ref exists, the reference again (guards against a stale fixture).
+  * and the reference again (guards against a stale fixture): live where oracle/_ref exists, else tests/golden/ref_digests.json.
 """
 import json
 import os
@@ -113,20 +113,26 @@ def test_nis_coef_tables_golden():
     np.testing.assert_allclose(u[:, :6].sum(1), 0.0, atol=2e-3)   # USM rows are DC-free
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 def test_fixture_is_fresh_against_reference():
-    R = O.ref()
-    for case in G["easu_con"]:
+    """the committed EASU constants and the oracle's f32 -> f16 truncation against the reference's own code (live where oracle/_ref is
+    built, else through its outputs stored in tests/golden/ref_digests.json)"""
+    from tests import refgold
+
+    def ref_con(iw, ih, ow, oh):
         con = np.zeros(16, np.uint32)
+        O.ref().ref_easu_con(con.ctypes.data_as(O.u32p), iw, ih, iw, ih, ow, oh)
+        return con
+    for case in G["easu_con"]:
         iw, ih = case["in"]
         ow, oh = case["out"]
-        R.ref_easu_con(con.ctypes.data_as(O.u32p), iw, ih, iw, ih, ow, oh)
-        assert np.array_equal(con, u32(case["con"]))
+        assert refgold.same_as_reference("easu_con/%d/%d/%d/%d" % (iw, ih, ow, oh), u32(case["con"]), lambda: ref_con(iw, ih, ow, oh))
     rng = np.random.default_rng(0)
+    fs = []
     for _ in range(2000):
         f = float((rng.uniform(1, 2) * 2.0 ** rng.integers(-40, 30)) * rng.choice([-1, 1]))
-        f = float(np.float32(f))
-        assert O.lib().ovo_f32_to_f16_trunc(f) == R.ref_f32_to_f16(f)
+        fs.append(float(np.float32(f)))
+    mine = np.array([O.lib().ovo_f32_to_f16_trunc(f) for f in fs], np.uint32)
+    assert refgold.same_as_reference("f32_to_f16_trunc/2000", mine, lambda: np.array([O.ref().ref_f32_to_f16(f) for f in fs], np.uint32))
 
 
 def test_unorm8_decode_two_op_form_is_correctly_rounded():

@@ -2,7 +2,7 @@
 
   * bit-exact against the committed golden vectors (outputs of the reference's own FsrEasuF/FsrRcasF
     bodies and shader entry points, tests/golden/fsr_vectors.npz);
-  * bit-exact against oracle/_ref on fresh random inputs where the reference is available;
+  * bit-exact against oracle/_ref on fresh random inputs (live where it is built, else through tests/golden/ref_digests.json);
   * the analytical invariants of SURVEY.md 8c.
 """
 import json
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from tests import synth
+from tests import refgold, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 V = np.load(os.path.join(HERE, "golden", "fsr_vectors.npz"))
@@ -42,7 +42,6 @@ def test_oracle_matches_golden(m):
     assert same_bits(rcas, V[name + "_rcas"])
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("seed", range(6))
 def test_oracle_matches_reference_random(seed):
     rng = np.random.default_rng(seed)
@@ -55,10 +54,11 @@ def test_oracle_matches_reference_random(seed):
     proj = tuple(rng.uniform(0.2, 0.8, 4))
     centre, rad = O.mask_constants(ow, oh, float(rng.uniform(0.2, 1.2)), proj, True, seed & 1)
     a = O.easu(img, ow, oh, con, centre, rad)
-    assert same_bits(a, O.ref_easu(img, ow, oh, con, centre, rad))
+    key = "fsr_random/%d/" % seed
+    assert refgold.same_as_reference(key + "easu", a, lambda: O.ref_easu(img, ow, oh, con, centre, rad))
     q = O.unorm8_to_float(O.float_to_unorm8(a))
     rcon = O.rcas_con(float(rng.uniform(0, 1)), seed & 1)
-    assert same_bits(O.rcas(q, rcon, centre, rad), O.ref_rcas(q, rcon, centre, rad))
+    assert refgold.same_as_reference(key + "rcas", O.rcas(q, rcon, centre, rad), lambda: O.ref_rcas(q, rcon, centre, rad))
 
 
 def test_unorm8_roundtrip():
@@ -166,7 +166,6 @@ def test_pipeline_u8_stages_and_alpha():
         O.fsr_pipeline_u8(img8, 64, 53, stages=2)  # sharpen-only needs equal sizes
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("ow,seed,mutated", [(160, 21, False), (240, 22, True), (156, 23, True)])
 def test_oracle_matches_reference_on_adversarial_patches(ow, seed, mutated):
     """The content the round-4 adversarial search lives on (tools/debug/easu_err_search.py: cancelling gradient directions next to
@@ -191,10 +190,11 @@ def test_oracle_matches_reference_on_adversarial_patches(ow, seed, mutated):
     con = O.easu_con(8 * g, 8 * g, ow, ow)
     centre, rad = O.mask_constants(ow, ow, 2.0, (0.5, 0.5, 0.5, 0.5), True, 0)
     a = O.easu(img, ow, ow, con, centre, rad)
-    assert same_bits(a, O.ref_easu(img, ow, ow, con, centre, rad))
+    key = "fsr_adversarial/%d/%d/%d/" % (ow, seed, mutated)
+    assert refgold.same_as_reference(key + "easu", a, lambda: O.ref_easu(img, ow, ow, con, centre, rad))
     q = O.unorm8_to_float(O.float_to_unorm8(a))
     rcon = O.rcas_con(0.9, 0)
-    assert same_bits(O.rcas(q, rcon, centre, rad), O.ref_rcas(q, rcon, centre, rad))
+    assert refgold.same_as_reference(key + "rcas", O.rcas(q, rcon, centre, rad), lambda: O.ref_rcas(q, rcon, centre, rad))
 
 
 # ---- natural content (round 6): the three fixtures of tests/golden/natural_*.npz -------------------------------------------------------
@@ -211,7 +211,6 @@ def test_oracle_matches_natural_golden(name):
     assert natural.oracle_digests(img) == gold[name]
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("name", ["cube", "portal", "hopper"])
 @pytest.mark.parametrize("ow,radius", [(341, 2.0), (341, 0.5), (333, 0.7), (512, 2.0)])
 def test_oracle_matches_reference_on_natural_content(name, ow, radius):
@@ -224,16 +223,17 @@ def test_oracle_matches_reference_on_natural_content(name, ow, radius):
     con = O.easu_con(256, 256, ow, ow)
     centre, rad = O.mask_constants(ow, ow, radius, (0.45, 0.55, 0.6, 0.5), True, 0)
     a = O.easu(img, ow, ow, con, centre, rad)
-    assert same_bits(a, O.ref_easu(img, ow, ow, con, centre, rad))
+    key = "natural/%s/%d/%g/" % (name, ow, radius)
+    assert refgold.same_as_reference(key + "easu", a, lambda: O.ref_easu(img, ow, ow, con, centre, rad))
     q = O.unorm8_to_float(O.float_to_unorm8(a))
     rcon = O.rcas_con(0.9, 0)
-    assert same_bits(O.rcas(q, rcon, centre, rad), O.ref_rcas(q, rcon, centre, rad))
-    cs, cu = O.ref_nis_coefs()
-    ok, cfg = O.ref_nis_scaler_config(0.9, 256, 256, ow, ow)
+    assert refgold.same_as_reference(key + "rcas", O.rcas(q, rcon, centre, rad), lambda: O.ref_rcas(q, rcon, centre, rad))
+    cs, cu = refgold.ref_nis_coefs()
+    ok, cfg = refgold.ref_nis_scaler_config(0.9, 256, 256, ow, ow)
     assert ok
     blk = O.nis_block(cfg, centre, rad, 0)
-    assert same_bits(O.nis_upscale(img, ow, ow, blk, cs, cu), O.ref_nis_upscale(img, ow, ow, blk, cs, cu))
-    ok, cfg = O.ref_nis_scaler_config(0.9, 256, 256, 256, 256)
+    assert refgold.same_as_reference(key + "nis_upscale", O.nis_upscale(img, ow, ow, blk, cs, cu), lambda: O.ref_nis_upscale(img, ow, ow, blk, cs, cu))
+    ok, cfg = refgold.ref_nis_scaler_config(0.9, 256, 256, 256, 256)
     c2, r2 = O.mask_constants(256, 256, radius, (0.45, 0.55, 0.6, 0.5), True, 0)
     blk = O.nis_block(cfg, c2, r2, 0)
-    assert same_bits(O.nis_sharpen(img, blk), O.ref_nis_sharpen(img, blk, cs, cu))
+    assert refgold.same_as_reference(key + "nis_sharpen", O.nis_sharpen(img, blk), lambda: O.ref_nis_sharpen(img, blk, cs, cu))

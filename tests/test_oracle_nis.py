@@ -7,7 +7,7 @@ import pytest
 
 import openvr_fsr_amd as A
 from oracle import oracle as O
-from tests import synth
+from tests import refgold, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 V = np.load(os.path.join(HERE, "golden", "nis_vectors.npz"))
@@ -37,26 +37,26 @@ def test_nis_oracle_matches_golden(m):
     assert same_bits(O.nis_sharpen(img, blk2), V[name + "_sharpen"])
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("seed", range(5))
 def test_nis_oracle_matches_reference_random(seed):
     rng = np.random.default_rng(100 + seed)
-    cs, cu = O.ref_nis_coefs()
+    cs, cu = refgold.ref_nis_coefs()
     w, h = int(rng.integers(16, 90)), int(rng.integers(16, 90))
     gen = [synth.structured_u8, synth.random_u8, synth.extremes_u8][seed % 3]
     src = O.unorm8_to_float(gen(w, h, seed))
     sharp = float(rng.uniform(0, 1))
     s = rng.uniform(0.5, 1.0)
     ow, oh = int(w / s), int(h / s)
-    ok, cfg = O.ref_nis_scaler_config(sharp, w, h, ow, oh)
+    ok, cfg = refgold.ref_nis_scaler_config(sharp, w, h, ow, oh)
     assert ok
     centre, rad = O.mask_constants(ow, oh, float(rng.uniform(0.3, 1.5)), tuple(rng.uniform(0.3, 0.7, 4)), True, seed & 1)
     blk = O.nis_block(cfg, centre, rad, seed & 1)
-    assert same_bits(O.nis_upscale(src, ow, oh, blk, cs, cu), O.ref_nis_upscale(src, ow, oh, blk, cs, cu))
-    ok, cfg = O.ref_nis_scaler_config(sharp, w, h, w, h)
+    key = "nis_random/%d/" % seed
+    assert refgold.same_as_reference(key + "nis_upscale", O.nis_upscale(src, ow, oh, blk, cs, cu), lambda: O.ref_nis_upscale(src, ow, oh, blk, cs, cu))
+    ok, cfg = refgold.ref_nis_scaler_config(sharp, w, h, w, h)
     centre, rad = O.mask_constants(w, h, float(rng.uniform(0.3, 1.5)), tuple(rng.uniform(0.3, 0.7, 4)), True, seed & 1)
     blk = O.nis_block(cfg, centre, rad, seed & 1)
-    assert same_bits(O.nis_sharpen(src, blk), O.ref_nis_sharpen(src, blk, cs, cu))
+    assert refgold.same_as_reference(key + "nis_sharpen", O.nis_sharpen(src, blk), lambda: O.ref_nis_sharpen(src, blk, cs, cu))
 
 
 def test_nis_invariants():
@@ -76,7 +76,6 @@ def test_nis_invariants():
     assert out.min() >= 0.0 and out.max() <= 1.0 and (out[..., 3] == 1.0).all()
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (no /root/reference on this box)")
 @pytest.mark.parametrize("seed", [6, 13, 20])
 def test_oracle_matches_reference_on_non_finite_texels(seed):
     """NaN / +-Inf / 1e30 texels (outside the parity contract of the LIBRARY, header "TEXEL VALUES") still have one answer in the reference's
@@ -92,18 +91,20 @@ def test_oracle_matches_reference_on_non_finite_texels(seed):
     ow, oh = int(iw / 0.75), int(ih / 0.75)
     img = P.content(6, iw, ih, seed, rng)
     assert np.isnan(img).any() and np.isinf(img).any()
-    cs, cu = O.ref_nis_coefs()
+    cs, cu = refgold.ref_nis_coefs()
     centre, rad = O.mask_constants(ow, oh, 2.0)
     con = O.easu_con(iw, ih, ow, oh)
     a = O.easu(img, ow, oh, con, centre, rad)
-    assert P.same_bits(a, O.ref_easu(img, ow, oh, con, centre, rad))
+    key = "non_finite/%d/" % seed
+    assert refgold.same_as_reference(key + "easu", a, lambda: O.ref_easu(img, ow, oh, con, centre, rad), nan_equal=True)
     rcon = O.rcas_con(0.6, 0)
-    assert P.same_bits(O.rcas(a, rcon, centre, rad), O.ref_rcas(a, rcon, centre, rad))
-    ok, cfg = O.ref_nis_scaler_config(0.5, iw, ih, ow, oh)
+    assert refgold.same_as_reference(key + "rcas", O.rcas(a, rcon, centre, rad), lambda: O.ref_rcas(a, rcon, centre, rad), nan_equal=True)
+    ok, cfg = refgold.ref_nis_scaler_config(0.5, iw, ih, ow, oh)
     assert ok
     blk = O.nis_block(cfg, centre, rad, 0)
-    assert P.same_bits(O.nis_upscale(img, ow, oh, blk, cs, cu), O.ref_nis_upscale(img, ow, oh, blk, cs, cu))
-    ok, cfg = O.ref_nis_scaler_config(0.5, iw, ih, iw, ih)
+    assert refgold.same_as_reference(key + "nis_upscale", O.nis_upscale(img, ow, oh, blk, cs, cu), lambda: O.ref_nis_upscale(img, ow, oh, blk, cs, cu),
+                                     nan_equal=True)
+    ok, cfg = refgold.ref_nis_scaler_config(0.5, iw, ih, iw, ih)
     c2, r2 = O.mask_constants(iw, ih, 2.0)
     blk = O.nis_block(cfg, c2, r2, 0)
-    assert P.same_bits(O.nis_sharpen(img, blk), O.ref_nis_sharpen(img, blk, cs, cu))
+    assert refgold.same_as_reference(key + "nis_sharpen", O.nis_sharpen(img, blk), lambda: O.ref_nis_sharpen(img, blk, cs, cu), nan_equal=True)
