@@ -84,12 +84,10 @@ __device__ __forceinline__ uint32_t unit_to_unorm10(float x) { return (uint32_t)
 // One fast-class add, one and, one compare per channel.  The product build's re-associated EASU differs from the
 // reference-order evaluation by at most 6.5e-4 byte (measured over 1e8 values incl. uniform-random and 0/255-only
 // content, profiles/r03_easu_err.txt; none above 2^-10 = 9.8e-4); the default band, 2^-9 = 1.95e-3, is 3 times that.
-#ifndef OVRFSR_TIE_BITS
-#define OVRFSR_TIE_BITS 9
-#endif
+constexpr int kTieBits = 9;
 __device__ __forceinline__ bool near_tie_byte(float v)
 {
-    constexpr int K = OVRFSR_TIE_BITS;
+    constexpr int K = kTieBits;
     static_assert(K >= 3 && K <= 12, "band half-width 2^-K byte");
     constexpr float bias = 256.0f + 1.0f / (float)(1 << K);
     constexpr uint32_t mask = ((1u << (K - 1)) - 1u) << (16 - K);
@@ -114,13 +112,11 @@ __device__ __forceinline__ float raw_max(float a, float b) { float r; __asm__("v
 // tolerance even behind RCAS's largest gain (the host derives xmin from the sharpness: 0.25 or 0.5; +inf when no sharpening
 // pass follows).  Rounds 2-3 tested |x - half(x)| against an ABSOLUTE 2^-17 per channel (7 VALU per channel, and no cover at
 // all above 2.0 where the spacing outgrows the band).
-#ifndef OVRFSR_TIE_HALF_BITS
-#define OVRFSR_TIE_HALF_BITS 6
-#endif
+constexpr int kTieHalfBits = 6;
 __device__ __forceinline__ uint32_t half_tie_code(float x, uint32_t xmin_bits)
 {
-    constexpr uint32_t W = 1u << (13 - OVRFSR_TIE_HALF_BITS);      // band half-width in units of 2^-13 spacing
-    static_assert(OVRFSR_TIE_HALF_BITS >= 2 && OVRFSR_TIE_HALF_BITS <= 12, "band = 2^-K of a half spacing");
+    constexpr uint32_t W = 1u << (13 - kTieHalfBits);      // band half-width in units of 2^-13 spacing
+    static_assert(kTieHalfBits >= 2 && kTieHalfBits <= 12, "band = 2^-K of a half spacing");
     constexpr uint32_t M = 0x1fffu & ~(2u * W - 1u);
     const uint32_t bits = __float_as_uint(x);
     // 0 iff x is inside the band AND x >= xmin: below xmin (and for negative x) the unsigned difference wraps or the sign bit is set
@@ -152,7 +148,7 @@ __device__ __forceinline__ bool near_tie_half_abs(float x, float band_pre /* 2^-
 }
 __device__ __forceinline__ bool near_tie_half3_hdr(float r, float g, float b, float xmin, float tmax)
 {
-    constexpr float kPre = 1.0f / (float)(1u << (1 + OVRFSR_TIE_HALF_BITS));
+    constexpr float kPre = 1.0f / (float)(1u << (1 + kTieHalfBits));
     if (tmax <= 1.0f) return near_tie_half3(r, g, b, xmin); // workgroup-uniform: unit-range footprints keep the binade-relative band
     const float bp = kPre * tmax;
     return (int)near_tie_half_abs(r, bp, xmin) | (int)near_tie_half_abs(g, bp, xmin) | (int)near_tie_half_abs(b, bp, xmin);

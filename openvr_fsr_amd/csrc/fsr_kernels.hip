@@ -77,8 +77,11 @@ static hipError_t easu_go(bool strict, const EasuArgs &a, dim3 grid, size_t lds,
 template <int I, int O>
 static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t s)
 {
-    // OVRFSR_RCAS_DPP=0: A/B switch back to the per-lane-loads kernel (diagnostic)
-    static const bool dpp = [] { const char *e = std::getenv("OVRFSR_RCAS_DPP"); return !(e && e[0] == '0'); }();
+#ifdef OVRFSR_RCAS_NO_DPP /* measurement build: the per-lane-loads kernel only (reference side of tests/test_gpu_parity.py's DPP equality test) */
+    constexpr bool dpp = false;
+#else
+    constexpr bool dpp = true;
+#endif
     const bool unmasked = !a.tileList && a.m.mode[0] == MASK_ALL_INSIDE && a.m.mode[1] == MASK_ALL_INSIDE;
     if (strict) {
         hipLaunchKernelGGL((ovrfsr_strict::rcas_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
@@ -88,11 +91,10 @@ static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t
             // small launches: the grid is r = workgroups / kRcasResident rounds of the resident workgroups, the last one partly filled;
             // half-height workgroups run ceil(2r) rounds of half the length (3 % more work per pixel).  One C2 eye image: r = 1.41,
             // 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us, profiles/r05_frame.txt); a batch: no difference, the
-            // 8-row form wins.  OVRFSR_RCAS_TH=16|32 forces one form (tuning)
-            static const int forced = [] { const char *e = std::getenv("OVRFSR_RCAS_TH"); return e ? std::atoi(e) : 0; }();
+            // 8-row form wins
             const uint64_t wgs = (uint64_t)tx * ty * grid.z;
             const uint64_t full = (wgs + kRcasResident - 1) / kRcasResident, half = (2 * wgs + kRcasResident - 1) / kRcasResident;
-            const bool small = forced ? forced == 16 : (wgs < 16 * kRcasResident && 103 * half < 200 * full);
+            const bool small = wgs < 16 * kRcasResident && 103 * half < 200 * full;
             if (small) {
                 const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
                 hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_kernel<O, false, 16>), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
@@ -221,12 +223,8 @@ hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const Fu
     const bool strict = prec == PREC_FP32_STRICT;
     if (!strict && easu_fast_pitch(a.cellsW) == 0) return hipErrorInvalidValue;
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
-    // OVRFSR_FUSED_LDS_PAD=<bytes> (diagnostic): extra dynamic LDS nobody touches -> fewer workgroups per CU; measures how the kernel's
-    // throughput follows its occupancy (profiles/r04_fused_variants.txt) before anyone rebuilds its planes to gain a workgroup
-    static const size_t pad = [] { const char *e = std::getenv("OVRFSR_FUSED_LDS_PAD"); const long v = e ? std::atol(e) : 0; return (size_t)(v > 0 ? v : 0); }();
-    const size_t need = fused_lds_bytes(prec, in_fmt, mid_fmt, a.cellsW, a.cellsH);
-    if (need > kFusedLdsMax) return hipErrorInvalidValue; // never launch with less LDS than the plane layout assumes (callers pre-check: PrepareResources)
-    const size_t lds = need + pad > kFusedLdsMax ? kFusedLdsMax : need + pad; // only the diagnostic pad is clamped
+    const size_t lds = fused_lds_bytes(prec, in_fmt, mid_fmt, a.cellsW, a.cellsH);
+    if (lds > kFusedLdsMax) return hipErrorInvalidValue; // never launch with less LDS than the plane layout assumes (callers pre-check: PrepareResources)
     OVRFSR_DISPATCH_FMT3(fused_go, mid_fmt, strict, a, grid, lds, s)
 }
 
@@ -280,10 +278,9 @@ hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt
     if (!a.tileList || !a.tileRec || !a.bilX || !a.bilY || nTiles == 0 || !outside_staged_ok(a.v, in_fmt)) return hipErrorInvalidValue;
     if (a.lds_cols < 2 || a.lds_cols > 36 || a.lds_rows < 2 || a.lds_rows > 34) return hipErrorInvalidValue;
     // persistent workgroups: block b walks list entries b, b + G, ... (G a multiple of 8: the list is XCD-banded, entry e
-    // belongs to band e % 8, so a workgroup stays in its XCD's band); OVRFSR_OUTSIDE_TPW = tiles per workgroup (tuning)
-    static const uint32_t tpw = [] { const char *e = std::getenv("OVRFSR_OUTSIDE_TPW"); const int v = e ? std::atoi(e) : 2; return (uint32_t)(v < 1 ? 1 : v); }();
+    // belongs to band e % 8, so a workgroup stays in its XCD's band), kOutsideTilesPerWg entries each
     a.nTiles = nTiles;
-    uint32_t G = ((nTiles + tpw - 1) / tpw + 7u) & ~7u;
+    uint32_t G = ((nTiles + kOutsideTilesPerWg - 1) / kOutsideTilesPerWg + 7u) & ~7u;
     if (G > nTiles) G = nTiles;
     const dim3 grid(G, 1, batch);
     if (tileH == 24) { OVRFSR_DISPATCH_FMT3(outside_staged_go24, mid_fmt, a, grid, s) }

@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256) void easu_kernel(const ovrfsr::EasuArgs a)
 // These re-associations change rounding only (measured max-abs vs the oracle: see tests).
 // ------------------------------------------------------------------------------------------------
 // e2_t: the two-vector type of the product resolve: packed (v_pk_*_f32 on 64-bit register pairs).  (The same expressions on two scalars
-// were measured in round 4 -- tools/variants/fsr_variants.patch (-DOVRFSR_EASU_SCALAR), profiles/r04_easu_scalar_ab.txt: 47 % more instructions, the same time.)
+// were measured in round 4 -- profiles/r04_easu_scalar_ab.txt: 47 % more instructions, the same time.)
 typedef f2_t e2_t;
 __device__ __forceinline__ e2_t mke2(float a, float b) { return mk2(a, b); }
 
@@ -399,7 +399,6 @@ __device__ __forceinline__ e2_t mke2(float a, float b) { return mk2(a, b); }
 // profiles/r04_easu_err_search.txt) -- and a dirR on the other side of the 1/32768 threshold would switch the whole kernel
 // shape.  With dir and dirR bit-identical to the reference's, everything downstream is well-conditioned and the re-associations
 // of the product build stay inside the band.  3 packed instructions and 1 scalar more than the contracted form.
-#ifndef OVRFSR_EASU_DIR_CONTRACTED /* measurement macro: the pre-round-4 form (packed FMAs) */
 __device__ __forceinline__ e2_t easu_dir_ref(const float4 &aF, const float4 &aG4, const float4 &aJ, const float4 &aK, float ws, float wt,
                                              float wu, float wv, float &dirR)
 {
@@ -415,21 +414,9 @@ __device__ __forceinline__ e2_t easu_dir_ref(const float4 &aF, const float4 &aG4
     dirR = dx2 + dy2;
     return dir;
 }
-#else
-__device__ __forceinline__ e2_t easu_dir_ref(const float4 &aF, const float4 &aG4, const float4 &aJ, const float4 &aK, float ws, float wt,
-                                             float wu, float wv, float &dirR)
-{
-    e2_t dir = mke2(aF.x, aF.y) * ws;
-    dir = mke2(aG4.x, aG4.y) * wt + dir;
-    dir = mke2(aJ.x, aJ.y) * wu + dir;
-    dir = mke2(aK.x, aK.y) * wv + dir;
-    dirR = dir.x * dir.x + dir.y * dir.y;
-    return dir;
-}
-#endif
 
 // colour-plane cell of the product kernels: float4 (R, G, B, 1).  (A plane of four halves per cell -- exact for the bytes of an RGBA8
-// texel and for RGBA16F texels -- was measured for the fused kernel in round 4: tools/variants/fsr_variants.patch (-DOVRFSR_FUSED_NARROW=1).)
+// texel and for RGBA16F texels -- was measured for the fused kernel in round 4: profiles/r04_fused_variants.txt.)
 __device__ __forceinline__ float4 ldc(OVRFSR_PTR_RC(float4) col, int i) { return col[i]; }
 __device__ __forceinline__ void stc(OVRFSR_PTR_R(float4) col, int i, float r, float g, float b) { col[i] = make_float4(r, g, b, 1.0f); }
 
@@ -872,11 +859,7 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
     OVRFSR_PTR(float) lum = OVRFSR_CARVE(float, reinterpret_cast<float *>(OVRFSR_RAW(ana) + ncell), ncell, PITCH * ovrfsr::kLumPadRows, K_EASU_LUM, smem, a.ldsBytes);
 
     // which stores the near-tie guard (below) covers
-#ifdef OVRFSR_TIE_OFF
-    constexpr bool kGuardU8 = false, kGuardH = false;
-#else
     constexpr bool kGuardU8 = byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8, kGuardH = OUT_FMT == ovrfsr::FMT_RGBA16F;
-#endif
     constexpr bool kGuard = kGuardU8 || kGuardH;
     // half stores of float sources: the largest |channel| of the staged footprint (HDR tiles widen the guard's band, near_tie_half3_hdr)
     constexpr bool kTmax = kGuardH && !byte_domain;
@@ -1058,11 +1041,7 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
             tie_append(tieB, ly + 1);
         }
     }
-#ifdef OVRFSR_TIE_NOPASS
-    if constexpr (false) { // measurement build: detection and listing only (wrong pixels: the listed ones are never stored)
-#else
     if constexpr (kGuard) {
-#endif
         if ((threadIdx.x & 63u) == 0u) tie_cnt[wave] = tie_n;
         __syncthreads();
         const uint32_t n0 = tie_cnt[0], n1 = tie_cnt[1], n2 = tie_cnt[2], total = n0 + n1 + n2 + tie_cnt[3];
@@ -1627,9 +1606,6 @@ __global__ __launch_bounds__(NT) OVRFSR_FUSED_OCC void fused_kernel(const ovrfsr
             const float fpx = floorf(ppx_raw), fpy = floorf(ppy_raw);
             base = ((int)fpy - tile_y0) * pitch + ((int)fpx - tile_x0); fppx = ppx_raw - fpx; fppy = ppy_raw - fpy;
         };
-#ifdef OVRFSR_TIE_NOPASS
-        if (a.v.outW < 0) {
-#else
         if (total <= (uint32_t)(NT / 8)) { // workgroup-uniform: few pixels -> four lanes per pixel (easu_resolve_quad), each writes its component
             const int q = (int)(threadIdx.x & 3u);
 #pragma unroll 1
@@ -1642,7 +1618,6 @@ __global__ __launch_bounds__(NT) OVRFSR_FUSED_OCC void fused_kernel(const ovrfsr
                 stm_comp(mid, i, q, o);
             }
         } else {
-#endif
 #pragma unroll 1
             for (uint32_t t = rot; t < total; t += (uint32_t)NT) { // one lane per listed pixel
                 int i, base; float fppx, fppy, r, gg, b;

@@ -19,12 +19,10 @@ constexpr int kThreads = 256;
 constexpr int kLumPadRows = 5;    // rows past the EASU luma plane that the 4-rows-per-lane analysis sweep may read (allocated, never written)
 // dynamic LDS the fused kernel may ask for: the 160 KiB of a CU minus its static LDS (row / column tables of stage 1, list counters: < 2 KiB)
 constexpr size_t kFusedLdsMax = 158 * 1024;
-#ifndef OVRFSR_FUSED_NT
-#define OVRFSR_FUSED_NT 256
-#endif
-constexpr int kFusedThreads = OVRFSR_FUSED_NT; // threads per workgroup of the product build's fused kernel (one 32x32 tile either way)
+constexpr int kFusedThreads = 256; // threads per workgroup of the fused kernel, one 32x32 tile (512: profiles/r03_fused_threads.txt)
 // fused kernel: waves x sweeps x 64 near-tie entries (uint16), kept in the luma plane
 constexpr size_t kFusedTieListBytes = (size_t)(kFusedThreads / 64) * (((kTileW + 2) * (kTileH + 2) + kFusedThreads - 1) / kFusedThreads) * 64 * 2;
+constexpr uint32_t kOutsideTilesPerWg = 2; // outside_staged_kernel: list entries each persistent workgroup walks
 constexpr int kOutsidePitch = 40; // outside_staged_kernel: floats per channel row of its planar LDS texel plane (>= 36 columns)
 constexpr int kRcasDppTileW = 62; // rcas_dpp_kernel: a wave = 64 consecutive columns, 62 stored (2 halo lanes)
 constexpr int kRcasDppTileH = 32; //                  4 waves x 8 rows per lane

@@ -111,7 +111,7 @@ __device__ __forceinline__ float4 nis_edge_map(const float q[9], float kDetectRa
 __device__ __forceinline__ int nis_coef_row(int phase) { return (((phase & 15) << 2) | (phase >> 4)) * 8; }
 
 // cell types of the x255 luma plane and the edge-map plane.  (The reference's NIS_USE_HALF_PRECISION mode, NIS_Scaler.h:133-148 -- these
-// two planes in half / half4, arithmetic in float -- was measured in round 3: 4.9e-3 off and half the speed, tools/variants/nis_variants.patch (-DOVRFSR_NIS_HALF_LDS).)
+// two planes in half / half4, arithmetic in float -- was measured in round 3: 4.9e-3 off and half the speed, profiles/r03_nis_variants.txt.)
 typedef float nis_lum_t;
 typedef float4 nis_edge_t;
 __device__ __forceinline__ float4 nis_edge_load(const float4 &e) { return e; }
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void nis_scaler_kernel(const ovrfsr::NisArgs a
     t.kSharpStrengthScale = a.kSharpStrengthScale; t.kSharpLimitMin = a.kSharpLimitMin; t.kSharpLimitScale = a.kSharpLimitScale;
 
     // (Round 4 measured this pixel loop in two passes with the edge lanes compacted into an LDS list: 10 % fewer VALU instructions, 11 %
-    // slower -- a barrier and a one-wave tail per workgroup, scattered LDS reads: tools/variants/nis_variants.patch (-DOVRFSR_NIS_COMPACT), profiles/r04_nis_compaction.txt.)
+    // slower -- a barrier and a one-wave tail per workgroup, scattered LDS reads: profiles/r04_nis_compaction.txt.)
     // product build, 4-byte output texels: lanes permuted so that every 16-lane ds_read_b128 group (the edge-map plane)
     // reads 16 consecutive cells (lane32_to_pos, fsr_device.inc); a row of 32 pixels stays one 128-byte store line
     const int lx = (OVRFSR_STRICT == 0 && TexelBytes<OUT_FMT>::v == 4) ? lane32_to_pos(threadIdx.x & 31) : (int)(threadIdx.x & 31);

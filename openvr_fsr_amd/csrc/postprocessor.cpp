@@ -43,11 +43,7 @@ static inline bool inject_failure() { return false; }
 #endif
 static inline hipError_t dev_malloc(void **p, size_t bytes) { return inject_failure() ? hipErrorOutOfMemory : hipMalloc(p, bytes); }
 static inline hipError_t event_create(hipEvent_t *e, unsigned flags) { return inject_failure() ? hipErrorOutOfMemory : hipEventCreateWithFlags(e, flags); }
-static inline hipError_t stream_create(hipStream_t *s, int prioMode, int least, int greatest)
-{
-    if (inject_failure()) return hipErrorOutOfMemory;
-    return prioMode == 0 ? hipStreamCreateWithFlags(s, hipStreamNonBlocking) : hipStreamCreateWithPriority(s, hipStreamNonBlocking, prioMode == 1 ? least : greatest);
-}
+static inline hipError_t stream_create(hipStream_t *s, int priority) { return inject_failure() ? hipErrorOutOfMemory : hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority); }
 
 // A stream that is being captured into a HIP graph takes launches and event fork / join only: an allocation or a table upload fails with
 // "operation not permitted when stream is capturing", INVALIDATES the caller's capture and, as a failed rebuild, used to leave the ctx
@@ -86,19 +82,21 @@ PostProcessor::PostProcessor(int device, const ovrfsr_config &cfg) : device_(dev
 //     latency-bound; round 3 rebuilt it.)
 //   * other sources (easu_outside_kernel / nis_outside_kernel: per-pixel, latency-bound, 8 workgroups per CU of spare issue slots
 //     beside the fused kernel's 3): YES -- C5 13.9 k against 10.3 k pairs/s at 128 images per call, 12.8 k against 10.6 k at 2.
-// `overlap` is that decision (OverlapOutside); OVRFSR_SERIAL=1 / 0 forces in-order / forked launches (diagnostic).
+// `overlap` is that decision (OverlapOutside).  -DOVRFSR_SERIAL (measurement build) launches everything in order on the caller's
+// stream, for stand-alone kernel timings (tools/debug/kt.sh, tools/debug/serial_vs_overlap.sh).
 hipStream_t PostProcessor::Fork(hipStream_t user, bool overlap)
 {
-    static const int serial = [] { const char *e = std::getenv("OVRFSR_SERIAL"); return e && e[0] == '1' ? 1 : e && e[0] == '0' ? 0 : -1; }();
-    if (serial == 1 || (serial < 0 && !overlap)) return user;
+#ifdef OVRFSR_SERIAL
+    overlap = false;
+#endif
+    if (!overlap) return user;
     if (!auxStream_) {
         // The auxiliary stream is a LOW-priority queue: what runs on it (the outside-tile kernel of half / float passes) fills the wave slots
         // the main kernel leaves, never the other way round -- C5 13.28 k / 13.30 k pairs/s at default priority, 13.32 k / 13.37 k low,
-        // 11.26 k / 11.29 k high (round 5).  OVRFSR_AUX_PRIORITY=default|high: tuning
-        static const int prio = [] { const char *e = std::getenv("OVRFSR_AUX_PRIORITY"); return !e ? 1 : e[0] == 'd' ? 0 : e[0] == 'h' ? 2 : 1; }();
+        // 11.26 k / 11.29 k high (round 5)
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const hipError_t ce = stream_create(&auxStream_, prio, least, greatest);
+        const hipError_t ce = stream_create(&auxStream_, least);
         if (ce != hipSuccess ||
             event_create(&evFork_, hipEventDisableTiming) != hipSuccess ||
             event_create(&evJoin_, hipEventDisableTiming) != hipSuccess) {

@@ -277,3 +277,13 @@ def test_product_never_touches_the_oracle():
         if src.endswith((".cpp", ".hpp", ".h", ".hip", ".inc")):
             text = open(os.path.join(root, "openvr_fsr_amd", "csrc", src)).read()
             assert '../../oracle' not in text and 'liboracle' not in text, src
+
+
+def test_no_environment_switch_in_the_shipped_library():
+    """No environment variable changes what the shipped library does inside a game process, except OVRFSR_LOG (the reference's
+    log line, header `OVRFSR_LOG`): measurement switches are build-time macros of variants that are never shipped."""
+    lib = os.path.join(ROOT, "openvr_fsr_amd", "libopenvr_fsr_amd.so")
+    if not os.path.exists(lib):
+        pytest.skip("libopenvr_fsr_amd.so is not built")
+    names = set(m.decode() for m in re.findall(rb"OVRFSR_[A-Z0-9_]+", open(lib, "rb").read()))
+    assert not names - {"OVRFSR_LOG"}, sorted(names)

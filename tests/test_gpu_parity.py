@@ -833,11 +833,13 @@ def test_rcas_dpp_kernel_equals_per_lane_loads_kernel(gpu):
     """rcas_dpp_kernel (side taps from neighbour lanes) and rcas_direct_kernel (every lane loads its own 14 taps) are the same
     arithmetic: identical bytes, including image borders and widths that are not a multiple of the 62-column wave tile -- on
     unmasked frames (regular 62 x 32 grid) and on the mask-sorted form of masked ones (segments of the inside runs, tinted copy
-    in the groups outside the radius).  OVRFSR_RCAS_DPP is read once per process, so each form runs in its own interpreter."""
+    in the groups outside the radius).  The per-lane-loads side is a measurement build of the library (-DOVRFSR_RCAS_NO_DPP, built on
+    demand like the audit build), so each form runs in its own interpreter."""
     import hashlib
     import os
     import subprocess
     import sys
+    from tests.variants import variant
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys, hashlib, numpy as np; sys.path.insert(0, %r)\n"
             "from tests import synth; from tests.util import run_gpu\n"
@@ -853,8 +855,7 @@ def test_rcas_dpp_kernel_equals_per_lane_loads_kernel(gpu):
             "            h.update(run_gpu(synth.structured_u8(iw, ih, 7 + eye), ow, oh, dt, eye=eye, out_width=ow, out_height=oh, sharpness=0.9, **kw).tobytes())\n"
             "print(h.hexdigest())\n") % root
     digests = []
-    for dpp in ("1", "0"):
-        env = dict(os.environ, OVRFSR_RCAS_DPP=dpp)
+    for env in (None, dict(os.environ, OVRFSR_LIB=variant("rcas_nodpp", "-DOVRFSR_RCAS_NO_DPP"))):
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         digests.append(r.stdout.strip().splitlines()[-1])

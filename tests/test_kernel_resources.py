@@ -110,7 +110,7 @@ def test_c5_pair_fits_one_simd(kernels):
     # LDS: three workgroups per CU.  Dynamic LDS at C5 (2370 -> 3160: the 34-row block's footprint is 29 texel rows at pitch 32):
     # colour + analysis + luma planes (36 B per cell) + kLumPadRows luma rows + the 34x34 float4 intermediate; static LDS of the shipped
     # kernel = the per-wave list counters and the footprint-maximum word of the HDR half guard (32 B; the 1.1 KB row / column tables belong to
-    # the item-walking measurement variant, tools/variants/fsr_variants.patch, not to this library)
+    # the item-walking measurement variant of round 4, profiles/r04_fused_variants.txt, not to this library)
     dynamic_c5 = 32 * 29 * 36 + 32 * 5 * 4 + 34 * 34 * 16
     for k, v in fused.items():
         assert v["group_segment_fixed_size"] <= 64, (k, v["group_segment_fixed_size"])

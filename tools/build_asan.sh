@@ -14,8 +14,13 @@ if [ "$1" = "--runtime" ]; then echo "$RT"; exit 0; fi
 if [ "$1" = "--runtime-gcc" ]; then echo "$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libubsan.so)"; exit 0; fi
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined"
 mkdir -p "$ROOT/ab"
-make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA="$SAN --offload-compress" LDEXTRA="-fsanitize=address,undefined" BUILD=build_asan OUT=../../ab/asan.so 2>&1 | grep -v "option-ignored\|^/opt/rocm\|^make" || true
-test -f "$ROOT/ab/asan.so"
+# a failed build leaves no library and no stamp behind (the stamp is written last, after every step succeeded)
+rm -f "$ROOT/ab/asan.so" "$ROOT/ab/asan.so.stamp"
+LOG="$ROOT/ab/asan.make.log"
+status=0
+make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA="$SAN --offload-compress" LDEXTRA="-fsanitize=address,undefined" BUILD=build_asan OUT=../../ab/asan.so >"$LOG" 2>&1 || status=$?
+grep -v "option-ignored\|^/opt/rocm\|^make" "$LOG" || true
+[ $status -eq 0 ] || exit $status
 ROCM=${ROCM_PATH:-/opt/rocm}
 for ex in headless bench_node thread_stress; do
     SRC="$ROOT/examples/$ex.c"; [ -f "$SRC" ] || SRC="$ROOT/tests/debug/$ex.c"   # (thread_stress.c lives with the tests)

@@ -12,8 +12,13 @@ RT=$(ls $ROCM/lib/llvm/lib/clang/*/lib/linux/libclang_rt.tsan-x86_64.so | head -
 if [ "$1" = "--runtime" ]; then echo "$RT"; exit 0; fi
 SAN="-fsanitize=thread -fno-omit-frame-pointer -gline-tables-only"
 mkdir -p "$ROOT/ab"
-make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA="$SAN --offload-compress" LDEXTRA="-fsanitize=thread" BUILD=build_tsan OUT=../../ab/tsan.so 2>&1 | grep -v "option-ignored\|^/opt/rocm\|^make" || true
-test -f "$ROOT/ab/tsan.so"
+# a failed build leaves no library and no stamp behind (the stamp is written last, after every step succeeded)
+rm -f "$ROOT/ab/tsan.so" "$ROOT/ab/tsan.so.stamp"
+LOG="$ROOT/ab/tsan.make.log"
+status=0
+make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA="$SAN --offload-compress" LDEXTRA="-fsanitize=thread" BUILD=build_tsan OUT=../../ab/tsan.so >"$LOG" 2>&1 || status=$?
+grep -v "option-ignored\|^/opt/rocm\|^make" "$LOG" || true
+[ $status -eq 0 ] || exit $status
 $CLANG -std=c11 -O1 $SAN -shared-libsan -pthread -D_POSIX_C_SOURCE=200809L -D__HIP_PLATFORM_AMD__ "$ROOT/tests/debug/thread_stress.c" -I"$ROOT/include" -I"$ROCM/include" \
     "$ROOT/ab/tsan.so" -L"$ROCM/lib" -lamdhip64 -lm -Wl,-rpath,"\$ORIGIN" -Wl,-rpath,"$ROCM/lib" -Wl,-rpath,"$(dirname "$RT")" -o "$ROOT/ab/thread_stress_tsan"
 python3 "$ROOT/tools/variant_fresh.py" --stamp tsan "$SAN"
