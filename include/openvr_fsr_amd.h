@@ -28,7 +28,7 @@ extern "C" {
 #define OVRFSR_API
 #endif
 
-#define OVRFSR_ABI_VERSION 5u /* 5: ovrfsr_pair_pending added; pair_submit pairs by arrival order; create / set_config validate the float fields.  4: ovrfsr_config::pair_submit (was reserved[0]; same struct size).  3: ovrfsr_apply_batch_shared added.  2: ovrfsr_average_gpu_time_ms added; precision value 1 (never built) removed */
+#define OVRFSR_ABI_VERSION 5u /* 5: ovrfsr_pair_pending added; pair_submit pairs by arrival order; create / set_config validate the float fields (multisampled inputs, OVRFSR_FORMAT_MS, came later without a version change: probe with one, an older library refuses it as OVRFSR_ERR_UNSUPPORTED).  4: ovrfsr_config::pair_submit (was reserved[0]; same struct size).  3: ovrfsr_apply_batch_shared added.  2: ovrfsr_average_gpu_time_ms added; precision value 1 (never built) removed */
 
 typedef enum ovrfsr_status {
     OVRFSR_OK = 0,
@@ -62,6 +62,29 @@ typedef enum ovrfsr_format {
     OVRFSR_FORMAT_RGB10A2_UNORM = 3,
     OVRFSR_FORMAT_BGRA8_UNORM = 4
 } ovrfsr_format;
+
+/* MULTISAMPLED INPUT (D3D11_TEXTURE2D_DESC::SampleDesc.Count > 1; the reference resolves such a texture into a single-sample copy of
+ * the input's own format before filtering: PrepareResources / GetInputView, PostProcessor.cpp:196-224,520-523).  The sample count
+ * travels in the high bits of ovrfsr_image::format: OVRFSR_FORMAT_MS(OVRFSR_FORMAT_RGBA8_UNORM, 4).  Samples 0 or 1 = single-sample;
+ * 2, 4 and 8 are accepted for every base format, for INPUT images only (a multisampled `out`, ovrfsr_save_ppm / ovrfsr_save_dds of
+ * one: OVRFSR_ERR_UNSUPPORTED); any other count or bit: OVRFSR_ERR_UNSUPPORTED.  A library older than this feature refuses every such
+ * value as an unknown format (OVRFSR_ERR_UNSUPPORTED): that is how a host probes for it, the ABI version is unchanged.
+ * Layout: samples interleaved per texel -- sample s of texel (x, y) at data + y*pitch_bytes + (x*S + s)*texel_bytes;
+ * pitch_bytes >= width*S*texel_bytes; alignment that of the base format; the 4 GiB span rule applies to the multisampled image.
+ * Resolve rule (D3D11 leaves resolve rounding to the implementation; this is the stated choice, the same in every build and
+ * precision), into the input's base format: UNORM channels (8-bit; RGB10A2's 10-bit RGB and 2-bit A) (sum_i k_i + S/2) >> log2 S in
+ * integers; RGBA16F / RGBA32F decoded to fp32, summed in sample order s0 + s1 + ... (no contraction, no re-association), multiplied by
+ * 1/S, half rounded to nearest even.  The result is what "resolve, then apply to the single-sample image" gives, bit for bit, on every
+ * path.  4x RGBA8 input on an unmasked product-build EASU pass with a UNORM8 destination (the two-kernel pipeline's intermediate, or an
+ * EASU-only UNORM8 output: C2's path) is resolved inside EASU's staging sweep, with the same integer rule, so nothing extra is written;
+ * every other multisampled input -- other formats and counts, masked / mask-sorted, cfg.fused = 1, NIS, RCAS-only, the strict build --
+ * takes a resolve kernel that writes a ctx-owned single-sample copy (BGRA8 re-ordered in the same pass) for the pipeline to run on.  A change
+ * of sample count is a format change (rebuild; refused under capture).  cfg.fsr_enabled = 0 forwards the multisampled descriptor
+ * untouched.  The debug-mode timer (ovrfsr_last_gpu_time_ms) includes the resolve, where the reference starts its query after
+ * ResolveSubresource (PostProcessor.cpp:574-581): where the resolve is fused into EASU's staging it cannot be timed apart, so the figure
+ * is the cost of the whole path from the submitted texture on every path. */
+#define OVRFSR_FORMAT_SAMPLES_SHIFT 8
+#define OVRFSR_FORMAT_MS(fmt, samples) ((uint32_t)(fmt) | ((uint32_t)(samples) << OVRFSR_FORMAT_SAMPLES_SHIFT))
 
 /* Arithmetic the kernels run in.  The reference only ever compiles the fp32 bodies
  * (`//#define A_HALF`, src/fsr/fsr_easu.hlsl:3).
@@ -115,7 +138,7 @@ typedef struct ovrfsr_image {
     uint32_t width;       /* texels                                                              */
     uint32_t height;      /* texels                                                              */
     uint32_t pitch_bytes; /* distance between rows; multiple of the texel size; >= width*texel   */
-    uint32_t format;      /* ovrfsr_format                                                       */
+    uint32_t format;      /* ovrfsr_format; inputs: | samples << OVRFSR_FORMAT_SAMPLES_SHIFT     */
 } ovrfsr_image;
 
 /* vr::VRTextureBounds_t, headers/openvr.h:609-613.  Only |uMax-uMin| > 0.5 is consulted

@@ -8,6 +8,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 FORMAT_RGBA8, FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGB10A2, FORMAT_BGRA8 = 0, 1, 2, 3, 4
+FORMAT_SAMPLES_SHIFT = 8  # OVRFSR_FORMAT_SAMPLES_SHIFT: multisampled inputs carry the sample count in the format's high bits
+
+
+def format_ms(fmt, samples):
+    """OVRFSR_FORMAT_MS(fmt, samples): the format value of a multisampled input image (samples 2, 4 or 8; 0 / 1 = single-sample)."""
+    return int(fmt) | int(samples) << FORMAT_SAMPLES_SHIFT
+
+
 PRECISION_FP32, PRECISION_FP32_STRICT = 0, 2
 EYE_LEFT, EYE_RIGHT = 0, 1
 

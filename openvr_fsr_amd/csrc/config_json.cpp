@@ -177,6 +177,14 @@ static bool capture_image_ok(const ovrfsr_image *img, uint32_t tb)
 // allocation owns nothing behind that)
 static size_t capture_span(const ovrfsr_image *img, uint32_t tb) { return (size_t)(img->height - 1) * img->pitch_bytes + (size_t)img->width * tb; }
 
+// The sample-count bits of a captured image (header, OVRFSR_FORMAT_MS): samples 0 / 1 are the base format; any other count (a multisampled
+// image -- the captures write single-sample images only -- or an unknown value) is OVRFSR_ERR_UNSUPPORTED.  *base = the format to save.
+static bool capture_format(uint32_t fmt, uint32_t *base)
+{
+    *base = fmt & ((1u << OVRFSR_FORMAT_SAMPLES_SHIFT) - 1u);
+    return (fmt >> OVRFSR_FORMAT_SAMPLES_SHIFT) <= 1u;
+}
+
 // Binary PPM (P6) of a device image; RGBA16F/32F/RGB10A2 are converted like a UNORM8 store.  Synchronises `stream`.
 static int save_ppm_impl(const ovrfsr_image *img, const char *path, void *stream);
 OVRFSR_API int ovrfsr_save_ppm(const ovrfsr_image *img, const char *path, void *stream)
@@ -189,6 +197,14 @@ OVRFSR_API int ovrfsr_save_ppm(const ovrfsr_image *img, const char *path, void *
 }
 static int save_ppm_impl(const ovrfsr_image *img, const char *path, void *stream)
 {
+    ovrfsr_image single;
+    if (img) {
+        uint32_t base;
+        if (!capture_format(img->format, &base)) return OVRFSR_ERR_UNSUPPORTED;
+        single = *img;
+        single.format = base;
+        img = &single;
+    }
     if (!img || !img->data || !path || img->format > OVRFSR_FORMAT_BGRA8_UNORM) return OVRFSR_ERR_INVALID_ARGUMENT;
     const bool ten = img->format == OVRFSR_FORMAT_RGB10A2_UNORM;
     const bool bgra = img->format == OVRFSR_FORMAT_BGRA8_UNORM;
@@ -223,6 +239,14 @@ static int save_ppm_impl(const ovrfsr_image *img, const char *path, void *stream
 // caps, height, width, pitch, pixel format FourCC 'DX10') + DDS_HEADER_DXT10 (DXGI format, TEXTURE2D, array size 1) + tightly packed rows.
 static int save_dds_impl(const ovrfsr_image *img, const char *path, void *stream)
 {
+    ovrfsr_image single;
+    if (img) {
+        uint32_t base;
+        if (!capture_format(img->format, &base)) return OVRFSR_ERR_UNSUPPORTED;
+        single = *img;
+        single.format = base;
+        img = &single;
+    }
     if (!img || !img->data || !path || img->format > OVRFSR_FORMAT_BGRA8_UNORM || img->width == 0 || img->height == 0) return OVRFSR_ERR_INVALID_ARGUMENT;
     // DXGI_FORMAT_R8G8B8A8_UNORM = 28, R16G16B16A16_FLOAT = 10, R32G32B32A32_FLOAT = 2, R10G10B10A2_UNORM = 24, B8G8R8A8_UNORM = 87
     static const uint32_t dxgi[5] = {28u, 10u, 2u, 24u, 87u}, bytes[5] = {4u, 8u, 16u, 4u, 4u};

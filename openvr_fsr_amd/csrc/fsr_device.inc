@@ -168,6 +168,23 @@ template <> struct TexelBytes<ovrfsr::FMT_RGBA8> { static constexpr int v = 4; }
 template <> struct TexelBytes<ovrfsr::FMT_RGBA16F> { static constexpr int v = 8; };
 template <> struct TexelBytes<ovrfsr::FMT_RGBA32F> { static constexpr int v = 16; };
 template <> struct TexelBytes<ovrfsr::FMT_RGB10A2> { static constexpr int v = 4; };
+template <> struct TexelBytes<ovrfsr::FMT_RGBA8_MS4> { static constexpr int v = 16; }; // one texel = its 4 samples
+
+// The multisample resolve rule of UNORM8 channels (header, OVRFSR_FORMAT_MS): per channel (sum + S/2) >> log2 S.  R+B and G+A sum as two
+// 16-bit lanes per dword (8 x 255 + 4 fits a lane; the shift moves nothing across the mask).  resolve_kernel and the resolving staging
+// sweep of easu_fast_kernel both call this: what the fused path stages is what the resolve pass writes.
+template <uint32_t S>
+__device__ __forceinline__ uint32_t resolve_unorm8(const uint32_t *v)
+{
+    constexpr uint32_t L = S == 2 ? 1u : S == 4 ? 2u : 3u;
+    uint32_t rb = (S / 2) * 0x00010001u, ga = rb;
+#pragma unroll
+    for (uint32_t sm = 0; sm < S; ++sm) {
+        rb += v[sm] & 0x00ff00ffu;
+        ga += (v[sm] >> 8) & 0x00ff00ffu;
+    }
+    return ((rb >> L) & 0x00ff00ffu) | (((ga >> L) & 0x00ff00ffu) << 8);
+}
 
 // The images and device tables of a kernel, declared through the checked accessors of fsr_bounds.h (plain pointers in the product build).
 // OVRFSR_IMAGES needs `a` (the kernel's argument block) and `img_i` in scope and declares `in` / `out`.

@@ -33,6 +33,102 @@ namespace ovrfsr_strict {
 #include "fsr_kernels.inc"
 #undef OVRFSR_STRICT
 } // namespace ovrfsr_strict
+
+// Resolve of a multisampled input (header, OVRFSR_FORMAT_MS): S samples per texel, interleaved, into a single-sample image of the base
+// format (BGRA8 re-ordered to RGBA8 in the same pass).  One rule for every build and precision, so one instantiation per format and S:
+// UNORM channels (sum + S/2) >> log2 S in integers; float channels summed in fp32 in sample order (contraction off), times 1/S (exact:
+// S is a power of two), half rounded to nearest even.  Memory-bound: every thread writes 16 bytes (16 / texel bytes texels) and reads
+// the S x 16 bytes behind them -- 16-byte loads where the source rows are 16-byte aligned (`vec`), texel loads otherwise and in the
+// last group of a row.  The destination rows are padded to 16 bytes (launch_resolve), so the store is always one 16-byte store; the
+// texels past the row's width that it writes land in that padding.
+namespace ovrfsr_fast {
+#pragma clang fp contract(off)
+template <int F, int S>
+__global__ __launch_bounds__(256) void resolve_kernel(const uint8_t *__restrict__ src, uint32_t srcPitch, uint64_t srcStride,
+                                                      uint8_t *__restrict__ dst, uint32_t dstPitch, uint32_t w, uint32_t h, uint32_t vec)
+{
+    constexpr uint32_t TB = F == ovrfsr::FMT_RGBA16F ? 8u : F == ovrfsr::FMT_RGBA32F ? 16u : 4u; // texel bytes
+    constexpr uint32_t T = 16u / TB;                                                             // texels per thread
+    constexpr uint32_t TW = TB / 4u;                                                             // dwords per texel
+    constexpr uint32_t L = S == 2 ? 1u : S == 4 ? 2u : 3u;
+    static_assert(S == 2 || S == 4 || S == 8, "2, 4 or 8 samples");
+    const uint32_t x0 = (blockIdx.x * 256u + threadIdx.x) * T, y = blockIdx.y, img = blockIdx.z;
+    if (x0 >= w) return;
+    OVRFSR_PTR(const uint8_t) s = OVRFSR_IMAGE(const uint8_t, src + (size_t)img * srcStride, srcPitch, (int)(w * S), (int)h, TB, K_IMAGE_IN);
+    OVRFSR_PTR(uint8_t) d = OVRFSR_IMAGE(uint8_t, dst, dstPitch, (int)(dstPitch / TB), (int)(h * gridDim.z), TB, K_IMAGE_OUT);
+    OVRFSR_PTR(const uint8_t) row = s + ((size_t)y * srcPitch + (size_t)x0 * S * TB);
+    uint32_t v[4 * S]; // sample sm of texel t: dwords [(t * S + sm) * TW, + TW)
+    if (vec && x0 + T <= w) {
+#pragma unroll
+        for (uint32_t k = 0; k < S; ++k) {
+            const uint4 q = *OVRFSR_AT(const uint4, row + 16u * k);
+            v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        }
+    } else {
+        const uint32_t n = min(T, w - x0);
+#pragma unroll
+        for (uint32_t t = 0; t < T; ++t)
+#pragma unroll
+            for (uint32_t sm = 0; sm < S; ++sm) {
+                uint32_t *p = v + (t * S + sm) * TW;
+                if (t < n) {
+                    OVRFSR_PTR(const uint8_t) q = row + (t * S + sm) * TB;
+                    if constexpr (TB == 4) { p[0] = *OVRFSR_AT(const uint32_t, q); }
+                    else if constexpr (TB == 8) { const uint2 u = *OVRFSR_AT(const uint2, q); p[0] = u.x; p[1] = u.y; }
+                    else { const uint4 u = *OVRFSR_AT(const uint4, q); p[0] = u.x; p[1] = u.y; p[2] = u.z; p[3] = u.w; }
+                } else {
+#pragma unroll
+                    for (uint32_t j = 0; j < TW; ++j) p[j] = 0u;
+                }
+            }
+    }
+    uint32_t o[4];
+    if constexpr (F == ovrfsr::FMT_RGBA8 || F == ovrfsr::FMT_BGRA8) {
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) {
+            uint32_t r = resolve_unorm8<S>(v + t * S);
+            if constexpr (F == ovrfsr::FMT_BGRA8) r = (r & 0xff00ff00u) | ((r >> 16) & 0xffu) | ((r & 0xffu) << 16); // B,G,R,A -> R,G,B,A
+            o[t] = r;
+        }
+    } else if constexpr (F == ovrfsr::FMT_RGB10A2) {
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) {
+            uint32_t r = S / 2, g = S / 2, b = S / 2, a = S / 2;
+#pragma unroll
+            for (uint32_t sm = 0; sm < S; ++sm) {
+                const uint32_t q = v[t * S + sm];
+                r += q & 0x3ffu; g += (q >> 10) & 0x3ffu; b += (q >> 20) & 0x3ffu; a += q >> 30;
+            }
+            o[t] = (r >> L) | ((g >> L) << 10) | ((b >> L) << 20) | ((a >> L) << 30);
+        }
+    } else if constexpr (F == ovrfsr::FMT_RGBA16F) {
+#pragma unroll
+        for (uint32_t t = 0; t < 2; ++t)
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+                float acc = 0.0f;
+#pragma unroll
+                for (uint32_t sm = 0; sm < S; ++sm) {
+                    const uint32_t dw = v[(t * S + sm) * 2 + (c >> 1)];
+                    const float f = (float)__builtin_bit_cast(_Float16, (uint16_t)(c & 1 ? dw >> 16 : dw & 0xffffu));
+                    acc = sm == 0 ? f : acc + f;
+                }
+                const uint32_t hb = __builtin_bit_cast(uint16_t, (_Float16)(acc * (1.0f / S)));
+                if (c & 1) o[2 * t + (c >> 1)] |= hb << 16;
+                else o[2 * t + (c >> 1)] = hb;
+            }
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < 4; ++c) {
+            float acc = __uint_as_float(v[c]);
+#pragma unroll
+            for (uint32_t sm = 1; sm < S; ++sm) acc = acc + __uint_as_float(v[sm * 4 + c]);
+            o[c] = __float_as_uint(acc * (1.0f / S));
+        }
+    }
+    *OVRFSR_AT(uint4, d + ((size_t)img * h + y) * dstPitch + (size_t)x0 * TB) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+} // namespace ovrfsr_fast
 #pragma clang fp contract(on)
 
 namespace ovrfsr {
@@ -330,6 +426,41 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
     return hipGetLastError();
 }
 
+uint32_t resolve_pitch(int fmt, uint32_t w)
+{
+    const uint32_t tb = fmt == FMT_RGBA16F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u;
+    return (w * tb + 15u) & ~15u;
+}
+
+template <int F>
+static void resolve_go(int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t dstPitch, uint32_t w,
+                       uint32_t h, uint32_t vec, dim3 grid, hipStream_t s)
+{
+    if (samples == 2) hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 2>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+    else if (samples == 4) hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 4>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+    else hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 8>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+}
+
+hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
+                          uint32_t batch, hipStream_t s)
+{
+    launch_fresh();
+    if (samples != 2 && samples != 4 && samples != 8) return hipErrorInvalidValue;
+    const uint32_t tb = fmt == FMT_RGBA16F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u, per = 256u * (16u / tb);
+    const uint32_t vec = ((uintptr_t)src % 16u == 0 && srcPitch % 16u == 0 && (batch < 2 || srcStride % 16u == 0)) ? 1u : 0u;
+    const uint32_t dstPitch = resolve_pitch(fmt, w);
+    const dim3 grid((w + per - 1) / per, h, batch);
+    switch (fmt) {
+    case FMT_RGBA8: resolve_go<FMT_RGBA8>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
+    case FMT_RGBA16F: resolve_go<FMT_RGBA16F>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
+    case FMT_RGBA32F: resolve_go<FMT_RGBA32F>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
+    case FMT_RGB10A2: resolve_go<FMT_RGB10A2>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
+    case FMT_BGRA8: resolve_go<FMT_BGRA8>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 #ifdef OVRFSR_BOUNDS
 // Drives the checked accessors through every kind of violation exactly once (tests/test_gpu_bounds.py asserts the counts): proof that a
 // zero from a campaign means "nothing out of bounds", not "nothing checked".  64 threads, 1024 bytes of dynamic LDS.
@@ -416,7 +547,18 @@ hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, 
     const bool strict = prec == PREC_FP32_STRICT;
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
     const size_t lds = easu_lds_bytes(prec, in_fmt, a.cellsW, a.cellsH);
+    if (in_fmt == FMT_RGBA8_MS4) { // resolve fused into the staging sweep: only where easu_msaa_fused_ok says so
+        const bool masked = a.tileList || a.m.mode[0] != MASK_ALL_INSIDE || a.m.mode[1] != MASK_ALL_INSIDE;
+        if (masked || !easu_msaa_fused_ok(prec, out_fmt, a.cellsW)) return hipErrorInvalidValue;
+        easu_fast_go<FMT_RGBA8_MS4, FMT_RGBA8, false>(easu_kernel_pitch(a.cellsW), a, grid, s);
+        return hipGetLastError();
+    }
     OVRFSR_DISPATCH_FMT(easu_go, strict, a, grid, lds, s)
+}
+
+bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW)
+{
+    return prec == PREC_FP32 && out_fmt == FMT_RGBA8 && easu_kernel_pitch(cellsW) != 0;
 }
 
 hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)

@@ -678,10 +678,10 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
     constexpr int SEGS = PITCH / 4;
     const int ncell = PITCH * cellsH;
     bool quad = false;
-    if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F)
+    if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4)
         quad = tile_x0 >= 0 && tile_y0 >= 0 && tile_x0 + PITCH <= inW && tile_y0 + cellsH <= inH; // pad columns are loaded too
     if (quad) {
-        if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F) {
+        if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4) {
             constexpr uint32_t TB = TexelBytes<IN_FMT>::v;
             OVRFSR_PTR_R(const uint8_t) base = img + ((size_t)tile_y0 * pitchB + (size_t)tile_x0 * TB); // uniform
             // (no loop vectorisation / interleaving in these sweeps: packing across iterations costs more in register
@@ -701,6 +701,18 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
                         stc(col, idx + j, rb, gb, bb);
                         const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
                         l[j] = b * 0.5f + (r * 0.5f + g); // ffx_fsr1.h:363 on the exact b/255 (see DESIGN "A parity lesson")
+                    }
+                } else if constexpr (IN_FMT == ovrfsr::FMT_RGBA8_MS4) {
+                    // 4-sample RGBA8: one 16-byte load per texel (its 4 samples), resolved before anything is staged -- then the RGBA8 body
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const u32x4_a4_t q = *OVRFSR_AT(const u32x4_a4_t, src + 16 * j);
+                        const uint32_t s4[4] = {q[0], q[1], q[2], q[3]};
+                        const uint32_t v = resolve_unorm8<4>(s4);
+                        const float rb = (float)(v & 0xffu), gb = (float)((v >> 8) & 0xffu), bb = (float)((v >> 16) & 0xffu);
+                        stc(col, idx + j, rb, gb, bb);
+                        const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
+                        l[j] = b * 0.5f + (r * 0.5f + g);
                     }
                 } else {
                     typedef half4_t half4_a8_t __attribute__((aligned(8)));
@@ -725,6 +737,15 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
             if constexpr (IN_FMT == ovrfsr::FMT_RGBA8) {
                 const uint32_t off = (uint32_t)sy * pitchB + (uint32_t)sx * 4u; // images are < 4 GiB (16384^2 x 4 B)
                 const uint32_t v = *OVRFSR_AT(const uint32_t, img + off);
+                const float rb = (float)(v & 0xffu), gb = (float)((v >> 8) & 0xffu), bb = (float)((v >> 16) & 0xffu);
+                stc(col, idx, rb, gb, bb);
+                const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
+                lum[idx] = b * 0.5f + (r * 0.5f + g);
+            } else if constexpr (IN_FMT == ovrfsr::FMT_RGBA8_MS4) {
+                const uint32_t off = (uint32_t)sy * pitchB + (uint32_t)sx * 16u; // the multisampled image spans <= 4 GiB (CheckImage)
+                const u32x4_a4_t q = *OVRFSR_AT(const u32x4_a4_t, img + off);
+                const uint32_t s4[4] = {q[0], q[1], q[2], q[3]};
+                const uint32_t v = resolve_unorm8<4>(s4);
                 const float rb = (float)(v & 0xffu), gb = (float)((v >> 8) & 0xffu), bb = (float)((v >> 16) & 0xffu);
                 stc(col, idx, rb, gb, bb);
                 const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
@@ -834,7 +855,7 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
     // per output row of the tile: sub-texel position ppy and the LDS cell index of the row of its 'f' texel.  Both are the
     // same for the 32 pixels of a row: 32 lanes compute them once (9 VALU) instead of every pixel.
     OVRFSR_LDS_ARRAY(float2, rowinfo, TH, K_EASU_ROWINFO);
-    constexpr bool byte_domain = IN_FMT == ovrfsr::FMT_RGBA8;
+    constexpr bool byte_domain = IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA8_MS4; // (MS4: resolved to RGBA8 as it is staged)
 
     const uint32_t img_i = blockIdx.z;
     const uint32_t tile = a.tileList ? OVRFSR_TILE_LIST(a)[blockIdx.x] : xcd_tile_index(blockIdx.x, a.tilesX * a.tilesY);

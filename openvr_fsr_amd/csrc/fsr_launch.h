@@ -22,6 +22,14 @@ size_t nis_scaler_lds_bytes(int cellsW, int cellsH);
 hipError_t launch_nis_scaler(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s, uint32_t nGroups = 0);
 hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
                               uint32_t batch, hipStream_t s);
+// multisampled input (OVRFSR_FORMAT_MS) -> single-sample image of the base format (BGRA8 -> RGBA8): image i of the batch at
+// dst + i * h * resolve_pitch(fmt, w), rows resolve_pitch(fmt, w) bytes apart (the row bytes rounded up to 16)
+uint32_t resolve_pitch(int fmt, uint32_t w);
+// 4-sample RGBA8 input resolved inside easu_fast_kernel's staging sweep (in_fmt FMT_RGBA8_MS4 of launch_easu): product build, unmasked,
+// UNORM8 destination (the pipeline's intermediate or an EASU-only output), a fixed LDS pitch
+bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW);
+hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
+                          uint32_t batch, hipStream_t s);
 bool outside_staged_ok(const BatchView &v, int in_fmt);
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a, uint32_t nGroups, uint32_t batch, hipStream_t s);

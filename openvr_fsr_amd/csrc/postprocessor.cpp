@@ -11,8 +11,21 @@
 
 namespace ovrfsr {
 
+// ovrfsr_image::format = base format | samples << OVRFSR_FORMAT_SAMPLES_SHIFT (header: multisampled input)
+static inline uint32_t base_format(uint32_t fmt) { return fmt & ((1u << OVRFSR_FORMAT_SAMPLES_SHIFT) - 1u); }
+static inline uint32_t format_samples(uint32_t fmt) { const uint32_t s = fmt >> OVRFSR_FORMAT_SAMPLES_SHIFT; return s > 1u ? s : 1u; }
+// the caller's image with a single-sample encoding (samples 0 or 1) reduced to its base format: one value per format from here on
+static inline ovrfsr_image canonical(const ovrfsr_image &img)
+{
+    ovrfsr_image c = img;
+    if (format_samples(c.format) == 1u) c.format = base_format(c.format);
+    return c;
+}
+
+// bytes of one texel (one SAMPLE of a multisampled image)
 static uint32_t texel_bytes(uint32_t fmt)
 {
+    fmt = base_format(fmt);
     return fmt == OVRFSR_FORMAT_RGBA8_UNORM || fmt == OVRFSR_FORMAT_RGB10A2_UNORM || fmt == OVRFSR_FORMAT_BGRA8_UNORM ? 4u
          : fmt == OVRFSR_FORMAT_RGBA16F ? 8u : 16u;
 }
@@ -162,6 +175,8 @@ void PostProcessor::ResetKeeping(bool keepRetired)
     initialized_ = false;
     if (swizzled_) (void)hipFree(swizzled_);
     swizzled_ = nullptr; swizzledBytes_ = 0;
+    if (resolved_) (void)hipFree(resolved_);
+    resolved_ = nullptr; resolvedBytes_ = 0;
     if (upscaled_) (void)hipFree(upscaled_);
     if (sharpened_) (void)hipFree(sharpened_);
     if (nisCoefDev_) (void)hipFree(nisCoefDev_);
@@ -194,14 +209,17 @@ int PostProcessor::SetConfig(const ovrfsr_config &cfg)
     return OVRFSR_OK;
 }
 
-int PostProcessor::CheckImage(const ovrfsr_image *img, const char *name)
+int PostProcessor::CheckImage(const ovrfsr_image *img, const char *name, bool input)
 {
     if (!img || !img->data) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, std::string(name) + ": null image");
-    if (img->format > OVRFSR_FORMAT_BGRA8_UNORM) return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": unknown format");
+    const uint32_t s = img->format >> OVRFSR_FORMAT_SAMPLES_SHIFT;
+    if (base_format(img->format) > OVRFSR_FORMAT_BGRA8_UNORM || (s > 1u && s != 2u && s != 4u && s != 8u))
+        return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": unknown format");
+    if (s > 1u && !input) return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": multisampled images are input-only");
     const uint32_t tb = texel_bytes(img->format);
     if (img->width == 0 || img->height == 0 || img->width > 16384 || img->height > 16384)
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, std::string(name) + ": bad size");
-    if (img->pitch_bytes < img->width * tb || (img->pitch_bytes % tb) != 0)
+    if ((uint64_t)img->pitch_bytes < (uint64_t)img->width * format_samples(img->format) * tb || (img->pitch_bytes % tb) != 0)
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, std::string(name) + ": bad pitch");
     // the fast paths address texels with 32-bit byte offsets off the image base (natural size: at most 16384^2 x 16 B = 4 GiB)
     if ((uint64_t)img->pitch_bytes * img->height > 0x100000000ull)
@@ -230,9 +248,11 @@ uint32_t PostProcessor::IntermediateFormat() const
     // Half-float pipelines (BASELINE C5) keep a half-float intermediate; quantize_intermediate=0 keeps fp32.
     if (!cfg_.quantize_intermediate) return OVRFSR_FORMAT_RGBA32F;
     // a 10-bit submission keeps 10-bit resources (DetermineOutputFormat, :63-74)
-    return inputFormat_ == OVRFSR_FORMAT_RGBA8_UNORM || inputFormat_ == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM
-         : inputFormat_ == OVRFSR_FORMAT_RGBA16F ? OVRFSR_FORMAT_RGBA16F
-         : inputFormat_ == OVRFSR_FORMAT_RGB10A2_UNORM ? OVRFSR_FORMAT_RGB10A2_UNORM : OVRFSR_FORMAT_RGBA32F;
+    // (inputFormat_ keeps a multisampled submission's encoding for the rebuild checks; its base format decides)
+    const uint32_t in = base_format(inputFormat_);
+    return in == OVRFSR_FORMAT_RGBA8_UNORM || in == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM
+         : in == OVRFSR_FORMAT_RGBA16F ? OVRFSR_FORMAT_RGBA16F
+         : in == OVRFSR_FORMAT_RGB10A2_UNORM ? OVRFSR_FORMAT_RGB10A2_UNORM : OVRFSR_FORMAT_RGBA32F;
 }
 
 void PostProcessor::PrepareUpscalingResources()
@@ -287,7 +307,8 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     inputWidth_ = submitted.width;
     inputHeight_ = submitted.height;
     inputFormat_ = submitted.format;
-    ovrfsr_image in = submitted; // what the kernels will see: a BGRA8 submission is re-ordered to RGBA8 first (ApplyPostProcess)
+    ovrfsr_image in = submitted; // what the kernels will see: a multisampled submission is resolved and a BGRA8 one re-ordered to RGBA8 first
+    in.format = base_format(in.format); // (ApplyPostProcess)
     if (in.format == OVRFSR_FORMAT_BGRA8_UNORM) in.format = OVRFSR_FORMAT_RGBA8_UNORM;
     uint32_t ow = 0, oh = 0;
     if (ovrfsr_output_size(&cfg_, in.width, in.height, &ow, &oh) != OVRFSR_OK || ow == 0 || oh == 0)
@@ -889,10 +910,54 @@ int PostProcessor::ApplySharpening(uint32_t n, int firstEye, int alternate, cons
 }
 
 // `in`/`out` describe image 0 of a batch of n; `out` is the FINAL destination.
+// 4-sample RGBA8 on C2's path -- product build, unmasked easu_fast_kernel, two-kernel pipeline with a UNORM8 intermediate or EASU-only into
+// UNORM8 -- is resolved inside EASU's staging sweep (FMT_RGBA8_MS4, the same resolve_unorm8 the resolve pass runs: identical staged bytes,
+// identical output); every other multisampled input takes the resolve pass.  -DOVRFSR_MSAA_RESOLVE_PASS (measurement build, never shipped)
+// sends this path through the resolve pass too: the A/B of profiles/msaa_c2.txt.
+bool PostProcessor::ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const
+{
+#ifdef OVRFSR_MSAA_RESOLVE_PASS
+    (void)in; (void)out;
+    return false;
+#else
+    const bool unmasked = !tileListDev_ && maskMode_[0] == MASK_ALL_INSIDE && maskMode_[1] == MASK_ALL_INSIDE;
+    const uint32_t easuOut = doSharpen_ ? IntermediateFormat() : out.format;
+    return in.format == (uint32_t)FMT_RGBA8_MS4 && doUpscale_ && !cfg_.use_nis && !useSorted_ && !useFused_ && unmasked &&
+           easu_msaa_fused_ok(cfg_.precision, (int)easuOut, cellsW_);
+#endif
+}
+
+// timerStarted: the caller (the multisample resolve below) has already recorded the debug-mode start event.
 int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                                    const ovrfsr_image &out, size_t outStride, hipStream_t stream)
+                                    const ovrfsr_image &out, size_t outStride, hipStream_t stream, bool timerStarted)
 {
     if (out.format == OVRFSR_FORMAT_BGRA8_UNORM) return Fail(OVRFSR_ERR_UNSUPPORTED, "BGRA8 is an input-only format");
+    const uint32_t samples = format_samples(in.format);
+    if (samples > 1u && !ResolveInStaging(in, out)) {
+        // the reference resolves a multisampled submission into a single-sample copy of its own format (PostProcessor.cpp:196-224,520-523):
+        // one resolve pass (BGRA8 re-ordered in it), then the single-sample pipeline on the copy.  The pairings the pipeline refuses are
+        // refused here, before anything is launched.
+        const uint32_t base = base_format(in.format);
+        ovrfsr_image single = in;
+        single.format = base == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : base;
+        single.pitch_bytes = resolve_pitch((int)base, in.width);
+        const bool inTen = single.format == OVRFSR_FORMAT_RGB10A2_UNORM, outTen = out.format == OVRFSR_FORMAT_RGB10A2_UNORM;
+        if ((outTen && !inTen) || (inTen && !outTen && out.format != OVRFSR_FORMAT_RGBA32F))
+            return Fail(OVRFSR_ERR_UNSUPPORTED, "RGB10A2 images pair with an RGB10A2 (or RGBA32F) destination only");
+        if (outTen && doUpscale_ && doSharpen_ && IntermediateFormat() != OVRFSR_FORMAT_RGB10A2_UNORM)
+            return Fail(OVRFSR_ERR_UNSUPPORTED, "RGB10A2 pipelines keep a 10-bit intermediate (quantize_intermediate = 1)");
+        const size_t one = (size_t)single.pitch_bytes * in.height;
+        int rcs = EnsureBuffer(&resolved_, &resolvedBytes_, one * n);
+        if (rcs != OVRFSR_OK) return rcs;
+        // the debug-mode timer brackets the resolve too (header: unlike the reference's query, which starts after ResolveSubresource)
+        const bool timing = cfg_.debug_mode && !capturing_ && queries_[kQueryCount - 1].end;
+        if (timing) (void)hipEventRecord(queries_[currentQuery_].start, stream);
+        hipError_t e = launch_resolve((int)base, (int)samples, static_cast<const uint8_t *>(in.data), in.pitch_bytes, inStride,
+                                      static_cast<uint8_t *>(resolved_), in.width, in.height, n, stream);
+        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("multisample resolve launch: ") + hipGetErrorString(e));
+        single.data = resolved_;
+        return ApplyPostProcess(n, firstEye, alternate, single, one, out, outStride, stream, timing);
+    }
     if (in.format == OVRFSR_FORMAT_BGRA8_UNORM) {
         // the reference reads B8G8R8A8 submissions through a typed view and writes R8G8B8A8 (PostProcessor.cpp:30-61,63-74):
         // re-order the channels once, then run the RGBA8 pipeline on the copy
@@ -916,7 +981,7 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
         return Fail(OVRFSR_ERR_UNSUPPORTED, "RGB10A2 pipelines keep a 10-bit intermediate (quantize_intermediate = 1)");
     // (the ring is complete: slots are created in order; a call that is being captured into a graph is not timed: its events could never be read back)
     const bool timing = cfg_.debug_mode && !capturing_ && queries_[kQueryCount - 1].end;
-    if (timing) (void)hipEventRecord(queries_[currentQuery_].start, stream);
+    if (timing && !timerStarted) (void)hipEventRecord(queries_[currentQuery_].start, stream);
     int rc = OVRFSR_OK;
     if (useSorted_) {
         rc = ApplySorted(n, firstEye, alternate, in, inStride, out, outStride, stream);
@@ -961,7 +1026,7 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
 {
     if (!enabled_) return Fail(OVRFSR_ERR_DISABLED, "post-processing disabled after an earlier failure; call reset");
     if (!out) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out is null");
-    int rc = CheckImage(in, "in");
+    int rc = CheckImage(in, "in", true);
     if (rc != OVRFSR_OK) return rc;
     if (eye != OVRFSR_EYE_LEFT && eye != OVRFSR_EYE_RIGHT) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "bad eye");
     static const ovrfsr_bounds defaultBounds = {0, 0, 1, 1};
@@ -971,6 +1036,8 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         *out = *in;
         return OVRFSR_OK;
     }
+    const ovrfsr_image inC = canonical(*in); // (a single-sample encoding of samples = 1 is its base format)
+    in = &inC;
     DeviceGuard guard(device_);
     if (guard.err != hipSuccess) return Fail(OVRFSR_ERR_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
 
@@ -1007,10 +1074,11 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         rc = CheckImage(out, "out");
         if (rc != OVRFSR_OK) return rc;
         if (out->width != outputWidth_ || out->height != outputHeight_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
-        dst = *out;
+        dst = canonical(*out);
     } else {
         dst.width = outputWidth_; dst.height = outputHeight_;
-        dst.format = in->format == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : in->format; // DetermineOutputFormat (:63-74)
+        const uint32_t inBase = base_format(in->format);
+        dst.format = inBase == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : inBase; // DetermineOutputFormat (:63-74)
         dst.pitch_bytes = dst.width * texel_bytes(dst.format);
         // (pair mode: both eyes' results are alive at once -- two ctx-owned images, left first)
         const size_t one = (size_t)dst.pitch_bytes * dst.height;
@@ -1100,10 +1168,13 @@ int PostProcessor::ApplyBatch(uint32_t n, int firstEye, int alternate, const ovr
     if (!enabled_) return Fail(OVRFSR_ERR_DISABLED, "post-processing disabled after an earlier failure; call reset");
     if (n == 0) return OVRFSR_OK;
     if (n > 65535) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "batch too large for one launch (65535)");
-    int rc = CheckImage(in0, "in0");
+    int rc = CheckImage(in0, "in0", true);
     if (rc != OVRFSR_OK) return rc;
     rc = CheckImage(out0, "out0");
     if (rc != OVRFSR_OK) return rc;
+    const ovrfsr_image inC = canonical(*in0), outC = canonical(*out0);
+    in0 = &inC;
+    out0 = &outC;
     if (!cfg_.fsr_enabled) return Fail(OVRFSR_ERR_DISABLED, "fsr_enabled is 0: nothing to launch");
     if (n > 1 && (inStride < (size_t)in0->pitch_bytes * in0->height || outStride < (size_t)out0->pitch_bytes * out0->height))
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "batch stride smaller than one image");

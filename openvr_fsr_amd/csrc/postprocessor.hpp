@@ -112,6 +112,8 @@ private:
     // ctx-owned device buffers: upscaledTexture / sharpenedTexture, PostProcessor.h:43-45,58-59
     void *swizzled_ = nullptr;          // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
     size_t swizzledBytes_ = 0;
+    void *resolved_ = nullptr;          // single-sample copy of a multisampled submission (rows padded to 16 B), see ApplyPostProcess
+    size_t resolvedBytes_ = 0;
     void *upscaled_ = nullptr;
     size_t upscaledBytes_ = 0;
     void *sharpened_ = nullptr;
@@ -131,7 +133,7 @@ private:
     void CollectQuery(hipStream_t stream);
 
     int Fail(int status, const std::string &what);
-    int CheckImage(const ovrfsr_image *img, const char *name);
+    int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled
     int PrepareResources(const ovrfsr_image &in);                         // :498-561
     void PrepareUpscalingResources();                                    // :285-383
     void PrepareSharpeningResources();                                   // :409-481
@@ -144,9 +146,10 @@ private:
     int EnsureBuffer(void **buf, size_t *have, size_t need);
     static bool RangesOverlap(const ovrfsr_image &in0, size_t inStride, const ovrfsr_image &out0, size_t outStride, uint32_t n);
     uint32_t IntermediateFormat() const;
+    bool ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const;
     float TieHalfMin() const;
     int ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                         const ovrfsr_image &out, size_t outStride, hipStream_t stream); // :563-638
+                         const ovrfsr_image &out, size_t outStride, hipStream_t stream, bool timerStarted = false); // :563-638
     int ApplyUpscaling(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
                        const ovrfsr_image &out, size_t outStride, hipStream_t stream);   // :385-401
     int ApplySorted(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,

@@ -14,7 +14,19 @@ _FMT_TORCH = {K.FORMAT_RGBA8: torch.uint8, K.FORMAT_RGBA16F: torch.float16, K.FO
 def image_of(t, fmt=None):
     """[H, W, 4] device tensor -> ovrfsr_image (no copy); ``fmt`` overrides the format implied by the dtype (e.g.
     K.FORMAT_BGRA8 for a uint8 tensor whose channel order is B,G,R,A).  A [H, W] int32 tensor is an R10G10B10A2_UNORM image (one packed
-    dword per texel: R bits 0-9, G 10-19, B 20-29, A 30-31)."""
+    dword per texel: R bits 0-9, G 10-19, B 20-29, A 30-31).  A [H, W, S, 4] tensor (or [H, W, S] int32) is a multisampled input with S
+    samples per texel, interleaved (K.format_ms); ``fmt`` then names its base format."""
+    if ((t.dim() == 4 and t.shape[3] == 4) or (t.dim() == 3 and t.dtype == torch.int32)) and t.shape[2] in (2, 4, 8):
+        if not t.is_cuda:
+            raise ValueError("expected a tensor on the GPU")
+        samples = t.shape[2]
+        flat = t.reshape(t.shape[0], t.shape[1] * samples, *t.shape[3:])  # a view: samples are contiguous within a row
+        if flat.data_ptr() != t.data_ptr() or (t.dim() == 4 and (t.stride(2) != 4 or t.stride(3) != 1)) or (t.dim() == 3 and t.stride(2) != 1):
+            raise ValueError("samples of a texel must be contiguous")
+        img = image_of(flat, fmt)
+        img.width = t.shape[1]
+        img.format = K.format_ms(img.format, samples)
+        return img
     if t.dim() == 2 and t.dtype == torch.int32 and t.is_cuda:
         if t.stride(1) != 1:
             raise ValueError("texels must be contiguous")
