@@ -28,7 +28,7 @@ extern "C" {
 #define OVRFSR_API
 #endif
 
-#define OVRFSR_ABI_VERSION 5u /* 5: ovrfsr_pair_pending added; pair_submit pairs by arrival order; create / set_config validate the float fields (multisampled inputs, OVRFSR_FORMAT_MS, came later without a version change: probe with one, an older library refuses it as OVRFSR_ERR_UNSUPPORTED).  4: ovrfsr_config::pair_submit (was reserved[0]; same struct size).  3: ovrfsr_apply_batch_shared added.  2: ovrfsr_average_gpu_time_ms added; precision value 1 (never built) removed */
+#define OVRFSR_ABI_VERSION 5u /* 5: ovrfsr_pair_pending added; pair_submit pairs by arrival order; create / set_config validate the float fields (multisampled inputs, OVRFSR_FORMAT_MS, came later without a version change: probe with one, an older library refuses it as OVRFSR_ERR_UNSUPPORTED; the same holds for the input format OVRFSR_FORMAT_R11G11B10F = 6).  4: ovrfsr_config::pair_submit (was reserved[0]; same struct size).  3: ovrfsr_apply_batch_shared added.  2: ovrfsr_average_gpu_time_ms added; precision value 1 (never built) removed */
 
 typedef enum ovrfsr_status {
     OVRFSR_OK = 0,
@@ -60,8 +60,31 @@ typedef enum ovrfsr_format {
     OVRFSR_FORMAT_RGBA16F = 1,
     OVRFSR_FORMAT_RGBA32F = 2,
     OVRFSR_FORMAT_RGB10A2_UNORM = 3,
-    OVRFSR_FORMAT_BGRA8_UNORM = 4
+    OVRFSR_FORMAT_BGRA8_UNORM = 4,
+    /* 5 is unassigned and refused (OVRFSR_ERR_UNSUPPORTED), on purpose: the tests use it as their example of an unknown format.  Do not
+     * renumber the next one to close the gap. */
+    OVRFSR_FORMAT_R11G11B10F = 6
 } ovrfsr_format;
+
+/* R11G11B10F (DXGI_FORMAT_R11G11B10_FLOAT: Unity's DefaultHDR render target and a common scene-colour format elsewhere).  INPUT-ONLY.
+ * One 32-bit word per texel: R in bits 0-10, G in bits 11-21, B in bits 22-31; 4-byte texels, data and pitch_bytes aligned to 4.  The
+ * reference views such a texture with its own format (TranslateTypelessFormats: `default: return format`, PostProcessor.cpp:30-48,206-220),
+ * lets the sampler decode it and writes R8G8B8A8_UNORM (:63-74).
+ * Decode rule: each channel is an unsigned float with a 5-bit exponent of bias 15 and a 6-bit (R, G) or 5-bit (B) mantissa, which is a
+ * half float without its sign bit and its low mantissa bits: channel = the half float whose bits are the channel's bits shifted left by
+ * 4 (R, G) or 5 (B).  That is exact for every code: denormals, +Inf (exponent 31, mantissa 0) and NaN included; the largest finite values
+ * are 65024 (R, G) and 64512 (B).  Alpha reads 1.0, as D3D11 defines for a missing channel (the filters never read it).
+ * The decode runs in the resolve pass in front of the pipeline, into a ctx-owned RGBA16F copy; everything behind it is the RGBA16F
+ * pipeline: an R11G11B10F submission gives, byte for byte, what the RGBA16F image holding the same values (alpha 1.0) gives, on every
+ * path and in every build -- same intermediate choices, same tolerances, same texel-value domain (no negative values exist; Inf and NaN
+ * codes fall under the texel-value clause below: outside the parity contract, inside the memory-safety one).  Destinations: those of
+ * an RGBA16F input (RGBA8, RGBA16F, RGBA32F); a ctx-owned output (out->data == NULL) is RGBA16F.  As an `out`, and for ovrfsr_save_ppm /
+ * ovrfsr_save_dds: OVRFSR_ERR_UNSUPPORTED (the float -> float11 rounding is left to the implementation by D3D, and the reference never
+ * writes the format); the ctx stays enabled.  OVRFSR_FORMAT_MS(OVRFSR_FORMAT_R11G11B10F, S), S = 2, 4, 8, is accepted with the
+ * multisampled layout below and the float resolve rule applied to the decoded samples (fp32 sum in sample order, times 1/S, half
+ * rounded to nearest even), in the same pass.  cfg.fsr_enabled = 0 forwards the descriptor untouched.  A library older than this format
+ * refuses it as OVRFSR_ERR_UNSUPPORTED: that is how a host probes for it, the ABI version is unchanged.  What the extra pass costs:
+ * profiles/r11g11b10f_c5.txt. */
 
 /* MULTISAMPLED INPUT (D3D11_TEXTURE2D_DESC::SampleDesc.Count > 1; the reference resolves such a texture into a single-sample copy of
  * the input's own format before filtering: PrepareResources / GetInputView, PostProcessor.cpp:196-224,520-523).  The sample count

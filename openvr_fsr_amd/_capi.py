@@ -8,6 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 FORMAT_RGBA8, FORMAT_RGBA16F, FORMAT_RGBA32F, FORMAT_RGB10A2, FORMAT_BGRA8 = 0, 1, 2, 3, 4
+FORMAT_R11G11B10F = 6  # OVRFSR_FORMAT_R11G11B10F: input-only packed float (5 is unassigned and refused: header)
 FORMAT_SAMPLES_SHIFT = 8  # OVRFSR_FORMAT_SAMPLES_SHIFT: multisampled inputs carry the sample count in the format's high bits
 
 

@@ -178,10 +178,12 @@ static bool capture_image_ok(const ovrfsr_image *img, uint32_t tb)
 static size_t capture_span(const ovrfsr_image *img, uint32_t tb) { return (size_t)(img->height - 1) * img->pitch_bytes + (size_t)img->width * tb; }
 
 // The sample-count bits of a captured image (header, OVRFSR_FORMAT_MS): samples 0 / 1 are the base format; any other count (a multisampled
-// image -- the captures write single-sample images only -- or an unknown value) is OVRFSR_ERR_UNSUPPORTED.  *base = the format to save.
+// image -- the captures write single-sample images only -- or an unknown value) is OVRFSR_ERR_UNSUPPORTED, and so is the input-only
+// R11G11B10F with any count; an unknown base value (5, 7, ...) keeps OVRFSR_ERR_INVALID_ARGUMENT from the check behind.  *base = the format to save.
 static bool capture_format(uint32_t fmt, uint32_t *base)
 {
     *base = fmt & ((1u << OVRFSR_FORMAT_SAMPLES_SHIFT) - 1u);
+    if (*base == OVRFSR_FORMAT_R11G11B10F) return false; // input-only (header): no capture of it, single-sample or multisampled
     return (fmt >> OVRFSR_FORMAT_SAMPLES_SHIFT) <= 1u;
 }
 

@@ -128,6 +128,70 @@ __global__ __launch_bounds__(256) void resolve_kernel(const uint8_t *__restrict_
     }
     *OVRFSR_AT(uint4, d + ((size_t)img * h + y) * dstPitch + (size_t)x0 * TB) = make_uint4(o[0], o[1], o[2], o[3]);
 }
+
+// R11G11B10F input (header, OVRFSR_FORMAT_R11G11B10F) unpacked to RGBA16F, S samples per texel (1 = single-sample) resolved on the way.
+// One 32-bit word per sample: R bits 0-10, G 11-21, B 22-31; every channel IS a half float without its sign and low mantissa bits
+// (5-bit exponent, bias 15): half bits = channel << 4 (R, G) or << 5 (B), exact for every code, denormals, Inf and NaN included; alpha
+// reads 1.0.  S > 1: the float rule of resolve_kernel on the decoded samples (fp32 sum in sample order, contraction off, times 1/S, half
+// rounded to nearest even).  The first resolve-type kernel whose source (4 bytes) and destination (8 bytes) texels differ in size: every
+// thread takes two texels -- 8 x S bytes in 16-byte loads (one 8-byte load at S = 1) where the source rows allow it (`vec`), word loads
+// otherwise and in the last group of an odd-width row -- and writes them as one 16-byte store into rows padded to 16 bytes.
+template <int S>
+__global__ __launch_bounds__(256) void packed_resolve_kernel(const uint8_t *__restrict__ src, uint32_t srcPitch, uint64_t srcStride,
+                                                             uint8_t *__restrict__ dst, uint32_t dstPitch, uint32_t w, uint32_t h, uint32_t vec)
+{
+    static_assert(S == 1 || S == 2 || S == 4 || S == 8, "1, 2, 4 or 8 samples");
+    const uint32_t x0 = (blockIdx.x * 256u + threadIdx.x) * 2u, y = blockIdx.y, img = blockIdx.z;
+    if (x0 >= w) return;
+    OVRFSR_PTR(const uint8_t) s = OVRFSR_IMAGE(const uint8_t, src + (size_t)img * srcStride, srcPitch, (int)(w * S), (int)h, 4u, K_IMAGE_IN);
+    OVRFSR_PTR(uint8_t) d = OVRFSR_IMAGE(uint8_t, dst, dstPitch, (int)(dstPitch / 8u), (int)(h * gridDim.z), 8u, K_IMAGE_OUT);
+    OVRFSR_PTR(const uint8_t) row = s + ((size_t)y * srcPitch + (size_t)x0 * S * 4u);
+    uint32_t v[2 * S]; // sample sm of texel t: word t * S + sm
+    if (vec && x0 + 2u <= w) {
+        if constexpr (S == 1) {
+            const uint2 q = *OVRFSR_AT(const uint2, row);
+            v[0] = q.x; v[1] = q.y;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < S / 2; ++k) {
+                const uint4 q = *OVRFSR_AT(const uint4, row + 16u * k);
+                v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+            }
+        }
+    } else {
+        const uint32_t n = min(2u, w - x0);
+#pragma unroll
+        for (uint32_t t = 0; t < 2; ++t)
+#pragma unroll
+            for (uint32_t sm = 0; sm < S; ++sm) v[t * S + sm] = t < n ? *OVRFSR_AT(const uint32_t, row + (t * S + sm) * 4u) : 0u;
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (uint32_t t = 0; t < 2; ++t) {
+        if constexpr (S == 1) {
+            const uint32_t q = v[t];
+            o[2 * t] = ((q & 0x7ffu) << 4) | ((q & 0x3ff800u) << 9);
+            o[2 * t + 1] = ((q >> 22) << 5) | 0x3c000000u;
+        } else {
+            float r = 0.0f, g = 0.0f, b = 0.0f;
+#pragma unroll
+            for (uint32_t sm = 0; sm < S; ++sm) {
+                const uint32_t q = v[t * S + sm];
+                const float fr = (float)__builtin_bit_cast(_Float16, (uint16_t)((q & 0x7ffu) << 4));
+                const float fg = (float)__builtin_bit_cast(_Float16, (uint16_t)(((q >> 11) & 0x7ffu) << 4));
+                const float fb = (float)__builtin_bit_cast(_Float16, (uint16_t)((q >> 22) << 5));
+                r = sm == 0 ? fr : r + fr;
+                g = sm == 0 ? fg : g + fg;
+                b = sm == 0 ? fb : b + fb;
+            }
+            const uint32_t hr = __builtin_bit_cast(uint16_t, (_Float16)(r * (1.0f / S))), hg = __builtin_bit_cast(uint16_t, (_Float16)(g * (1.0f / S)));
+            const uint32_t hb = __builtin_bit_cast(uint16_t, (_Float16)(b * (1.0f / S)));
+            o[2 * t] = hr | (hg << 16);
+            o[2 * t + 1] = hb | 0x3c000000u; // alpha: S ones summed, times 1/S
+        }
+    }
+    *OVRFSR_AT(uint4, d + ((size_t)img * h + y) * dstPitch + (size_t)x0 * 8u) = make_uint4(o[0], o[1], o[2], o[3]);
+}
 } // namespace ovrfsr_fast
 #pragma clang fp contract(on)
 
@@ -426,10 +490,12 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
     return hipGetLastError();
 }
 
+// texel bytes of the resolve pass's destination: the source's own, except R11G11B10F (4-byte words in, RGBA16F out)
+static uint32_t resolve_dst_texel(int fmt) { return fmt == FMT_RGBA16F || fmt == FMT_R11G11B10F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u; }
+
 uint32_t resolve_pitch(int fmt, uint32_t w)
 {
-    const uint32_t tb = fmt == FMT_RGBA16F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u;
-    return (w * tb + 15u) & ~15u;
+    return (w * resolve_dst_texel(fmt) + 15u) & ~15u;
 }
 
 template <int F>
@@ -445,6 +511,18 @@ hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t src
                           uint32_t batch, hipStream_t s)
 {
     launch_fresh();
+    if (fmt == FMT_R11G11B10F) { // unpack (and resolve): two texels per thread, 8 x samples source bytes each
+        if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return hipErrorInvalidValue;
+        const uint32_t al = samples == 1 ? 8u : 16u;
+        const uint32_t vec = ((uintptr_t)src % al == 0 && srcPitch % al == 0 && (batch < 2 || srcStride % al == 0)) ? 1u : 0u;
+        const uint32_t dstPitch = resolve_pitch(fmt, w);
+        const dim3 grid((w + 511u) / 512u, h, batch);
+        if (samples == 1) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<1>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+        else if (samples == 2) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<2>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+        else if (samples == 4) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<4>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+        else hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<8>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+        return hipGetLastError();
+    }
     if (samples != 2 && samples != 4 && samples != 8) return hipErrorInvalidValue;
     const uint32_t tb = fmt == FMT_RGBA16F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u, per = 256u * (16u / tb);
     const uint32_t vec = ((uintptr_t)src % 16u == 0 && srcPitch % 16u == 0 && (batch < 2 || srcStride % 16u == 0)) ? 1u : 0u;

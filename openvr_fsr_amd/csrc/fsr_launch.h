@@ -24,6 +24,8 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
                               uint32_t batch, hipStream_t s);
 // multisampled input (OVRFSR_FORMAT_MS) -> single-sample image of the base format (BGRA8 -> RGBA8): image i of the batch at
 // dst + i * h * resolve_pitch(fmt, w), rows resolve_pitch(fmt, w) bytes apart (the row bytes rounded up to 16)
+// fmt FMT_R11G11B10F (samples 1, 2, 4 or 8): 4-byte packed texels in, RGBA16F texels out -- the one source whose destination texel
+// has another size: resolve_pitch(FMT_R11G11B10F, w) is the pitch of the 8-byte copy
 uint32_t resolve_pitch(int fmt, uint32_t w);
 // 4-sample RGBA8 input resolved inside easu_fast_kernel's staging sweep (in_fmt FMT_RGBA8_MS4 of launch_easu): product build, unmasked,
 // UNORM8 destination (the pipeline's intermediate or an EASU-only output), a fixed LDS pitch

@@ -9,6 +9,8 @@ namespace ovrfsr {
 
 enum : int { FMT_RGBA8 = 0, FMT_RGBA16F = 1, FMT_RGBA32F = 2, FMT_RGB10A2 = 3 };
 enum : int { FMT_BGRA8 = 4 }; // input-only: the multisample resolve kernel's source (re-ordered to RGBA8 as it resolves)
+// input-only: R11G11B10F (one packed word per texel; 5 is unassigned, as in the header), the resolve pass's source only: unpacked to RGBA16F there
+enum : int { FMT_R11G11B10F = 6 };
 // input-only: 4-sample RGBA8 (= OVRFSR_FORMAT_MS(OVRFSR_FORMAT_RGBA8_UNORM, 4)), resolved inside easu_fast_kernel's staging sweep
 enum : int { FMT_RGBA8_MS4 = 0x400 };
 enum : int { PREC_FP32 = 0, PREC_FP32_STRICT = 2 }; // ovrfsr_precision (1 is not a mode)

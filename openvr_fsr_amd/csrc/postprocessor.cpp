@@ -26,7 +26,8 @@ static inline ovrfsr_image canonical(const ovrfsr_image &img)
 static uint32_t texel_bytes(uint32_t fmt)
 {
     fmt = base_format(fmt);
-    return fmt == OVRFSR_FORMAT_RGBA8_UNORM || fmt == OVRFSR_FORMAT_RGB10A2_UNORM || fmt == OVRFSR_FORMAT_BGRA8_UNORM ? 4u
+    return fmt == OVRFSR_FORMAT_RGBA8_UNORM || fmt == OVRFSR_FORMAT_RGB10A2_UNORM || fmt == OVRFSR_FORMAT_BGRA8_UNORM ||
+                   fmt == OVRFSR_FORMAT_R11G11B10F ? 4u
          : fmt == OVRFSR_FORMAT_RGBA16F ? 8u : 16u;
 }
 
@@ -213,8 +214,10 @@ int PostProcessor::CheckImage(const ovrfsr_image *img, const char *name, bool in
 {
     if (!img || !img->data) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, std::string(name) + ": null image");
     const uint32_t s = img->format >> OVRFSR_FORMAT_SAMPLES_SHIFT;
-    if (base_format(img->format) > OVRFSR_FORMAT_BGRA8_UNORM || (s > 1u && s != 2u && s != 4u && s != 8u))
+    const uint32_t base = base_format(img->format); // (5 is unassigned: header)
+    if ((base > OVRFSR_FORMAT_BGRA8_UNORM && base != OVRFSR_FORMAT_R11G11B10F) || (s > 1u && s != 2u && s != 4u && s != 8u))
         return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": unknown format");
+    if (base == OVRFSR_FORMAT_R11G11B10F && !input) return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": R11G11B10F is an input-only format");
     if (s > 1u && !input) return Fail(OVRFSR_ERR_UNSUPPORTED, std::string(name) + ": multisampled images are input-only");
     const uint32_t tb = texel_bytes(img->format);
     if (img->width == 0 || img->height == 0 || img->width > 16384 || img->height > 16384)
@@ -251,7 +254,7 @@ uint32_t PostProcessor::IntermediateFormat() const
     // (inputFormat_ keeps a multisampled submission's encoding for the rebuild checks; its base format decides)
     const uint32_t in = base_format(inputFormat_);
     return in == OVRFSR_FORMAT_RGBA8_UNORM || in == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM
-         : in == OVRFSR_FORMAT_RGBA16F ? OVRFSR_FORMAT_RGBA16F
+         : in == OVRFSR_FORMAT_RGBA16F || in == OVRFSR_FORMAT_R11G11B10F ? OVRFSR_FORMAT_RGBA16F // (R11G11B10F: unpacked to RGBA16F first)
          : in == OVRFSR_FORMAT_RGB10A2_UNORM ? OVRFSR_FORMAT_RGB10A2_UNORM : OVRFSR_FORMAT_RGBA32F;
 }
 
@@ -310,6 +313,7 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     ovrfsr_image in = submitted; // what the kernels will see: a multisampled submission is resolved and a BGRA8 one re-ordered to RGBA8 first
     in.format = base_format(in.format); // (ApplyPostProcess)
     if (in.format == OVRFSR_FORMAT_BGRA8_UNORM) in.format = OVRFSR_FORMAT_RGBA8_UNORM;
+    if (in.format == OVRFSR_FORMAT_R11G11B10F) in.format = OVRFSR_FORMAT_RGBA16F; // unpacked in the resolve pass: the RGBA16F route from here on
     uint32_t ow = 0, oh = 0;
     if (ovrfsr_output_size(&cfg_, in.width, in.height, &ow, &oh) != OVRFSR_OK || ow == 0 || oh == 0)
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "output size is zero or beyond 16384 texels (render_scale must be finite and > 0)");
@@ -932,14 +936,17 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
                                     const ovrfsr_image &out, size_t outStride, hipStream_t stream, bool timerStarted)
 {
     if (out.format == OVRFSR_FORMAT_BGRA8_UNORM) return Fail(OVRFSR_ERR_UNSUPPORTED, "BGRA8 is an input-only format");
+    if (base_format(out.format) == OVRFSR_FORMAT_R11G11B10F) return Fail(OVRFSR_ERR_UNSUPPORTED, "R11G11B10F is an input-only format");
     const uint32_t samples = format_samples(in.format);
-    if (samples > 1u && !ResolveInStaging(in, out)) {
+    const bool packedFloat = base_format(in.format) == OVRFSR_FORMAT_R11G11B10F;
+    if ((samples > 1u || packedFloat) && !ResolveInStaging(in, out)) {
         // the reference resolves a multisampled submission into a single-sample copy of its own format (PostProcessor.cpp:196-224,520-523):
         // one resolve pass (BGRA8 re-ordered in it), then the single-sample pipeline on the copy.  The pairings the pipeline refuses are
-        // refused here, before anything is launched.
+        // refused here, before anything is launched.  An R11G11B10F submission of any sample count, 1 included, takes the same pass: it
+        // unpacks the words to an RGBA16F copy (the sampler's decode in the reference: header), 8-byte texels from 4-byte ones.
         const uint32_t base = base_format(in.format);
         ovrfsr_image single = in;
-        single.format = base == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : base;
+        single.format = base == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : packedFloat ? OVRFSR_FORMAT_RGBA16F : base;
         single.pitch_bytes = resolve_pitch((int)base, in.width);
         const bool inTen = single.format == OVRFSR_FORMAT_RGB10A2_UNORM, outTen = out.format == OVRFSR_FORMAT_RGB10A2_UNORM;
         if ((outTen && !inTen) || (inTen && !outTen && out.format != OVRFSR_FORMAT_RGBA32F))
@@ -1078,7 +1085,8 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
     } else {
         dst.width = outputWidth_; dst.height = outputHeight_;
         const uint32_t inBase = base_format(in->format);
-        dst.format = inBase == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : inBase; // DetermineOutputFormat (:63-74)
+        // DetermineOutputFormat (:63-74); an R11G11B10F submission gets what the RGBA16F image of the same values gets (header)
+        dst.format = inBase == OVRFSR_FORMAT_BGRA8_UNORM ? OVRFSR_FORMAT_RGBA8_UNORM : inBase == OVRFSR_FORMAT_R11G11B10F ? OVRFSR_FORMAT_RGBA16F : inBase;
         dst.pitch_bytes = dst.width * texel_bytes(dst.format);
         // (pair mode: both eyes' results are alive at once -- two ctx-owned images, left first)
         const size_t one = (size_t)dst.pitch_bytes * dst.height;

@@ -112,7 +112,7 @@ private:
     // ctx-owned device buffers: upscaledTexture / sharpenedTexture, PostProcessor.h:43-45,58-59
     void *swizzled_ = nullptr;          // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
     size_t swizzledBytes_ = 0;
-    void *resolved_ = nullptr;          // single-sample copy of a multisampled submission (rows padded to 16 B), see ApplyPostProcess
+    void *resolved_ = nullptr;          // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one (rows padded to 16 B), see ApplyPostProcess
     size_t resolvedBytes_ = 0;
     void *upscaled_ = nullptr;
     size_t upscaledBytes_ = 0;
@@ -133,7 +133,7 @@ private:
     void CollectQuery(hipStream_t stream);
 
     int Fail(int status, const std::string &what);
-    int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled
+    int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled / R11G11B10F
     int PrepareResources(const ovrfsr_image &in);                         // :498-561
     void PrepareUpscalingResources();                                    // :285-383
     void PrepareSharpeningResources();                                   // :409-481

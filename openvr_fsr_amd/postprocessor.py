@@ -14,7 +14,8 @@ _FMT_TORCH = {K.FORMAT_RGBA8: torch.uint8, K.FORMAT_RGBA16F: torch.float16, K.FO
 def image_of(t, fmt=None):
     """[H, W, 4] device tensor -> ovrfsr_image (no copy); ``fmt`` overrides the format implied by the dtype (e.g.
     K.FORMAT_BGRA8 for a uint8 tensor whose channel order is B,G,R,A).  A [H, W] int32 tensor is an R10G10B10A2_UNORM image (one packed
-    dword per texel: R bits 0-9, G 10-19, B 20-29, A 30-31).  A [H, W, S, 4] tensor (or [H, W, S] int32) is a multisampled input with S
+    dword per texel: R bits 0-9, G 10-19, B 20-29, A 30-31); with ``fmt`` = K.FORMAT_R11G11B10F it is an R11G11B10_FLOAT image (input-only:
+    R bits 0-10, G 11-21, B 22-31).  A [H, W, S, 4] tensor (or [H, W, S] int32) is a multisampled input with S
     samples per texel, interleaved (K.format_ms); ``fmt`` then names its base format."""
     if ((t.dim() == 4 and t.shape[3] == 4) or (t.dim() == 3 and t.dtype == torch.int32)) and t.shape[2] in (2, 4, 8):
         if not t.is_cuda:
@@ -30,7 +31,9 @@ def image_of(t, fmt=None):
     if t.dim() == 2 and t.dtype == torch.int32 and t.is_cuda:
         if t.stride(1) != 1:
             raise ValueError("texels must be contiguous")
-        return K.Image(t.data_ptr(), t.shape[1], t.shape[0], t.stride(0) * 4, K.FORMAT_RGB10A2)
+        if fmt not in (None, K.FORMAT_RGB10A2, K.FORMAT_R11G11B10F):
+            raise ValueError("a packed int32 tensor is an RGB10A2 or an R11G11B10F image")
+        return K.Image(t.data_ptr(), t.shape[1], t.shape[0], t.stride(0) * 4, K.FORMAT_RGB10A2 if fmt is None else fmt)
     if t.dim() != 3 or t.shape[2] != 4 or not t.is_cuda:
         raise ValueError("expected a [H, W, 4] tensor on the GPU")
     if t.stride(2) != 1 or t.stride(1) != 4:
