@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "../../include/openvr_fsr_amd.h"
+#include "fsr_formats.h"
 
 namespace {
 
@@ -182,9 +183,9 @@ static size_t capture_span(const ovrfsr_image *img, uint32_t tb) { return (size_
 // R11G11B10F with any count; an unknown base value (5, 7, ...) keeps OVRFSR_ERR_INVALID_ARGUMENT from the check behind.  *base = the format to save.
 static bool capture_format(uint32_t fmt, uint32_t *base)
 {
-    *base = fmt & ((1u << OVRFSR_FORMAT_SAMPLES_SHIFT) - 1u);
+    *base = ovrfsr::base_format(fmt);
     if (*base == OVRFSR_FORMAT_R11G11B10F) return false; // input-only (header): no capture of it, single-sample or multisampled
-    return (fmt >> OVRFSR_FORMAT_SAMPLES_SHIFT) <= 1u;
+    return ovrfsr::format_samples(fmt) == 1u;
 }
 
 // Binary PPM (P6) of a device image; RGBA16F/32F/RGB10A2 are converted like a UNORM8 store.  Synchronises `stream`.
@@ -210,7 +211,7 @@ static int save_ppm_impl(const ovrfsr_image *img, const char *path, void *stream
     if (!img || !img->data || !path || img->format > OVRFSR_FORMAT_BGRA8_UNORM) return OVRFSR_ERR_INVALID_ARGUMENT;
     const bool ten = img->format == OVRFSR_FORMAT_RGB10A2_UNORM;
     const bool bgra = img->format == OVRFSR_FORMAT_BGRA8_UNORM;
-    const size_t tb = img->format == OVRFSR_FORMAT_RGBA8_UNORM || ten || bgra ? 4 : img->format == OVRFSR_FORMAT_RGBA16F ? 8 : 16;
+    const size_t tb = ovrfsr::texel_bytes(img->format);
     if (!capture_image_ok(img, (uint32_t)tb)) return OVRFSR_ERR_INVALID_ARGUMENT;
     std::vector<unsigned char> host(capture_span(img, (uint32_t)tb));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -251,8 +252,8 @@ static int save_dds_impl(const ovrfsr_image *img, const char *path, void *stream
     }
     if (!img || !img->data || !path || img->format > OVRFSR_FORMAT_BGRA8_UNORM || img->width == 0 || img->height == 0) return OVRFSR_ERR_INVALID_ARGUMENT;
     // DXGI_FORMAT_R8G8B8A8_UNORM = 28, R16G16B16A16_FLOAT = 10, R32G32B32A32_FLOAT = 2, R10G10B10A2_UNORM = 24, B8G8R8A8_UNORM = 87
-    static const uint32_t dxgi[5] = {28u, 10u, 2u, 24u, 87u}, bytes[5] = {4u, 8u, 16u, 4u, 4u};
-    const uint32_t tb = bytes[img->format];
+    static const uint32_t dxgi[5] = {28u, 10u, 2u, 24u, 87u};
+    const uint32_t tb = ovrfsr::texel_bytes(img->format);
     if (!capture_image_ok(img, tb)) return OVRFSR_ERR_INVALID_ARGUMENT;
     const uint32_t rowBytes = img->width * tb;
     std::vector<unsigned char> host(capture_span(img, tb));

@@ -200,6 +200,24 @@ __device__ __forceinline__ void poison(void *base, unsigned long long bytes)
     for (unsigned long long i = (bytes & ~3ull) + threadIdx.x; i < bytes; i += blockDim.x) b[i] = 0xffu;
     __syncthreads();
 }
+
+// HOST: the current device's counters of the including translation unit (g_counts has internal linkage: each kernel file exports a reader
+// that calls this), ADDED into out[kSlots] -- the first-hit record copied if `out` has none yet -- and optionally cleared
+static inline hipError_t read_counts(unsigned long long *out, bool reset)
+{
+    unsigned long long c[kSlots];
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(c, HIP_SYMBOL(g_counts), sizeof c);
+    if (e != hipSuccess) return e;
+    for (int i = 0; i < kFirstRec; ++i) out[i] += c[i];
+    if (out[kFirstRec] == 0 && c[kFirstRec] != 0)
+        for (int i = kFirstRec; i < kSlots; ++i) out[i] = c[i];
+    if (reset) {
+        for (unsigned long long &v : c) v = 0;
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_counts), c, sizeof c);
+    }
+    return e;
+}
 } // namespace ovrfsr_chk
 
 #define OVRFSR_PTR(T) ovrfsr_chk::ptr<T>                                   /* a pointer variable / parameter */

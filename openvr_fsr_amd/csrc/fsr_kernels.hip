@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "fsr_params.h"
 #include "fsr_launch.h"
+#include "fsr_formats.h"
 #include "fsr_bounds.h"
 
 #ifdef OVRFSR_TIE_AUDIT
@@ -273,41 +274,6 @@ static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t
     return hipGetLastError();
 }
 
-#define OVRFSR_DISPATCH_FMT(FN, ...)                                                                     \
-    switch (in_fmt < 3 && out_fmt < 3 ? in_fmt * 3 + out_fmt : -1) {                                                                      \
-    case 0: return FN<FMT_RGBA8, FMT_RGBA8>(__VA_ARGS__);                                                \
-    case 1: return FN<FMT_RGBA8, FMT_RGBA16F>(__VA_ARGS__);                                              \
-    case 2: return FN<FMT_RGBA8, FMT_RGBA32F>(__VA_ARGS__);                                              \
-    case 3: return FN<FMT_RGBA16F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 4: return FN<FMT_RGBA16F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 5: return FN<FMT_RGBA16F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    case 6: return FN<FMT_RGBA32F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 7: return FN<FMT_RGBA32F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 8: return FN<FMT_RGBA32F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    default: break;                                                                                      \
-    }                                                                                                    \
-    /* R10G10B10A2: only what the reference's 10-bit path needs (10-bit in -> 10-bit out, PostProcessor.cpp:63-74) plus a \
-       float destination for un-quantised parity checks */                                               \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGB10A2) return FN<FMT_RGB10A2, FMT_RGB10A2>(__VA_ARGS__); \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGBA32F) return FN<FMT_RGB10A2, FMT_RGBA32F>(__VA_ARGS__); \
-    return hipErrorInvalidValue;
-
-// the same without the 10-bit pairs: kernels that are not built for R10G10B10A2 (fused, LDS-staged outside)
-#define OVRFSR_DISPATCH_FMT3(FN, ...)                                                                     \
-    switch (in_fmt < 3 && out_fmt < 3 ? in_fmt * 3 + out_fmt : -1) {                                                                      \
-    case 0: return FN<FMT_RGBA8, FMT_RGBA8>(__VA_ARGS__);                                                \
-    case 1: return FN<FMT_RGBA8, FMT_RGBA16F>(__VA_ARGS__);                                              \
-    case 2: return FN<FMT_RGBA8, FMT_RGBA32F>(__VA_ARGS__);                                              \
-    case 3: return FN<FMT_RGBA16F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 4: return FN<FMT_RGBA16F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 5: return FN<FMT_RGBA16F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    case 6: return FN<FMT_RGBA32F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 7: return FN<FMT_RGBA32F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 8: return FN<FMT_RGBA32F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    default: break;                                                                                      \
-    }                                                                                                    \
-    return hipErrorInvalidValue;
-
 // LDS of the fused kernel: EASU planes + 34x34 intermediate (float4 cells)
 size_t fused_lds_bytes(int prec, int in_fmt, int mid_fmt, int cellsW, int cellsH)
 {
@@ -385,7 +351,7 @@ hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const Fu
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
     const size_t lds = fused_lds_bytes(prec, in_fmt, mid_fmt, a.cellsW, a.cellsH);
     if (lds > kFusedLdsMax) return hipErrorInvalidValue; // never launch with less LDS than the plane layout assumes (callers pre-check: PrepareResources)
-    OVRFSR_DISPATCH_FMT3(fused_go, mid_fmt, strict, a, grid, lds, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, fused_go, mid_fmt, strict, a, grid, lds, s)
 }
 
 template <int I, int O>
@@ -443,9 +409,9 @@ hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt
     uint32_t G = ((nTiles + kOutsideTilesPerWg - 1) / kOutsideTilesPerWg + 7u) & ~7u;
     if (G > nTiles) G = nTiles;
     const dim3 grid(G, 1, batch);
-    if (tileH == 24) { OVRFSR_DISPATCH_FMT3(outside_staged_go24, mid_fmt, a, grid, s) }
+    if (tileH == 24) { OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, outside_staged_go24, mid_fmt, a, grid, s) }
     if (tileH != 32) return hipErrorInvalidValue;
-    OVRFSR_DISPATCH_FMT3(outside_staged_go32, mid_fmt, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, outside_staged_go32, mid_fmt, a, grid, s)
 }
 
 // nTiles blocks, each resolving tile a.tileList[block]: tiles entirely outside the radius (product build only).
@@ -462,7 +428,7 @@ hipError_t launch_easu_outside(int in_fmt, int mid_fmt, int out_fmt, const EasuA
         return launch_outside_staged(kTileH, in_fmt, mid_fmt, out_fmt, o, nTiles, batch, s);
     }
     const dim3 grid(nTiles, 1, batch);
-    OVRFSR_DISPATCH_FMT(easu_outside_go, mid_fmt, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_outside_go, mid_fmt, a, grid, s)
 }
 
 // B8G8R8A8 -> R8G8B8A8 into a tightly packed buffer (dst pitch = 4*w, image stride = 4*w*h): a byte shuffle, 16 texels
@@ -490,53 +456,59 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
     return hipGetLastError();
 }
 
-// texel bytes of the resolve pass's destination: the source's own, except R11G11B10F (4-byte words in, RGBA16F out)
-static uint32_t resolve_dst_texel(int fmt) { return fmt == FMT_RGBA16F || fmt == FMT_R11G11B10F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u; }
-
+// rows of the resolve pass's destination: texels of the format the pipeline sees (R11G11B10F: 4-byte words in, RGBA16F out), padded to 16 bytes
 uint32_t resolve_pitch(int fmt, uint32_t w)
 {
-    return (w * resolve_dst_texel(fmt) + 15u) & ~15u;
+    return (w * texel_bytes(pipeline_format((uint32_t)fmt)) + 15u) & ~15u;
 }
 
-template <int F>
-static void resolve_go(int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t dstPitch, uint32_t w,
-                       uint32_t h, uint32_t vec, dim3 grid, hipStream_t s)
+// one launch of the resolve pass: what both resolve kernels take, and where they run
+struct ResolveJob {
+    const uint8_t *src; uint32_t srcPitch; uint64_t srcStride; uint8_t *dst; uint32_t dstPitch, w, h, vec;
+    dim3 grid; hipStream_t s;
+};
+template <int F, int S>
+static void resolve_launch(const ResolveJob &j)
 {
-    if (samples == 2) hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 2>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-    else if (samples == 4) hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 4>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-    else hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, 8>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
+    if constexpr (F == FMT_R11G11B10F)
+        hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<S>), j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
+    else
+        hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, S>), j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
+}
+// the kernel of the run-time sample count; false: no kernel is built for it (one sample: R11G11B10F only, which is unpacked whatever the count)
+template <int F>
+static bool resolve_go(int samples, const ResolveJob &j)
+{
+    switch (samples) {
+    case 1: if constexpr (F == FMT_R11G11B10F) { resolve_launch<F, 1>(j); return true; } else return false;
+    case 2: resolve_launch<F, 2>(j); return true;
+    case 4: resolve_launch<F, 4>(j); return true;
+    case 8: resolve_launch<F, 8>(j); return true;
+    default: return false;
+    }
 }
 
 hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
                           uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    if (fmt == FMT_R11G11B10F) { // unpack (and resolve): two texels per thread, 8 x samples source bytes each
-        if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return hipErrorInvalidValue;
-        const uint32_t al = samples == 1 ? 8u : 16u;
-        const uint32_t vec = ((uintptr_t)src % al == 0 && srcPitch % al == 0 && (batch < 2 || srcStride % al == 0)) ? 1u : 0u;
-        const uint32_t dstPitch = resolve_pitch(fmt, w);
-        const dim3 grid((w + 511u) / 512u, h, batch);
-        if (samples == 1) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<1>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-        else if (samples == 2) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<2>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-        else if (samples == 4) hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<4>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-        else hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<8>), grid, dim3(256), 0, s, src, srcPitch, srcStride, dst, dstPitch, w, h, vec);
-        return hipGetLastError();
-    }
-    if (samples != 2 && samples != 4 && samples != 8) return hipErrorInvalidValue;
-    const uint32_t tb = fmt == FMT_RGBA16F ? 8u : fmt == FMT_RGBA32F ? 16u : 4u, per = 256u * (16u / tb);
-    const uint32_t vec = ((uintptr_t)src % 16u == 0 && srcPitch % 16u == 0 && (batch < 2 || srcStride % 16u == 0)) ? 1u : 0u;
-    const uint32_t dstPitch = resolve_pitch(fmt, w);
-    const dim3 grid((w + per - 1) / per, h, batch);
+    // every thread writes 16 bytes: 16 / texel bytes texels, read from samples x 16 source bytes -- R11G11B10F (unpack, and resolve): two
+    // texels, 8 x samples source bytes (one 8-byte load at one sample)
+    const bool packed = fmt == FMT_R11G11B10F;
+    const uint32_t per = 256u * (packed ? 2u : 16u / texel_bytes((uint32_t)fmt)), al = packed && samples == 1 ? 8u : 16u;
+    const uint32_t vec = ((uintptr_t)src % al == 0 && srcPitch % al == 0 && (batch < 2 || srcStride % al == 0)) ? 1u : 0u;
+    const ResolveJob j{src, srcPitch, srcStride, dst, resolve_pitch(fmt, w), w, h, vec, dim3((w + per - 1) / per, h, batch), s};
+    bool launched = false; // stays false for a format or a sample count no kernel is built for
     switch (fmt) {
-    case FMT_RGBA8: resolve_go<FMT_RGBA8>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
-    case FMT_RGBA16F: resolve_go<FMT_RGBA16F>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
-    case FMT_RGBA32F: resolve_go<FMT_RGBA32F>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
-    case FMT_RGB10A2: resolve_go<FMT_RGB10A2>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
-    case FMT_BGRA8: resolve_go<FMT_BGRA8>(samples, src, srcPitch, srcStride, dst, dstPitch, w, h, vec, grid, s); break;
-    default: return hipErrorInvalidValue;
+    case FMT_R11G11B10F: launched = resolve_go<FMT_R11G11B10F>(samples, j); break;
+    case FMT_RGBA8: launched = resolve_go<FMT_RGBA8>(samples, j); break;
+    case FMT_RGBA16F: launched = resolve_go<FMT_RGBA16F>(samples, j); break;
+    case FMT_RGBA32F: launched = resolve_go<FMT_RGBA32F>(samples, j); break;
+    case FMT_RGB10A2: launched = resolve_go<FMT_RGB10A2>(samples, j); break;
+    case FMT_BGRA8: launched = resolve_go<FMT_BGRA8>(samples, j); break;
+    default: break;
     }
-    return hipGetLastError();
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 #ifdef OVRFSR_BOUNDS
@@ -578,22 +550,7 @@ hipError_t bounds_selftest()
     (void)hipFree(img);
     return e;
 }
-static hipError_t bounds_read_tu(unsigned long long *out, bool reset)
-{
-    unsigned long long c[ovrfsr_chk::kSlots];
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(c, HIP_SYMBOL(ovrfsr_chk::g_counts), sizeof c);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < ovrfsr_chk::kFirstRec; ++i) out[i] += c[i];
-    if (out[ovrfsr_chk::kFirstRec] == 0 && c[ovrfsr_chk::kFirstRec] != 0)
-        for (int i = ovrfsr_chk::kFirstRec; i < ovrfsr_chk::kSlots; ++i) out[i] = c[i];
-    if (reset) {
-        for (unsigned long long &v : c) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(ovrfsr_chk::g_counts), c, sizeof c);
-    }
-    return e;
-}
-hipError_t bounds_read_fsr(unsigned long long *out, bool reset) { return bounds_read_tu(out, reset); }
+hipError_t bounds_read_fsr(unsigned long long *out, bool reset) { return ovrfsr_chk::read_counts(out, reset); }
 #else
 hipError_t bounds_read_fsr(unsigned long long *, bool) { return hipErrorNotSupported; }
 hipError_t bounds_selftest() { return hipErrorNotSupported; }
@@ -631,7 +588,7 @@ hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, 
         easu_fast_go<FMT_RGBA8_MS4, FMT_RGBA8, false>(easu_kernel_pitch(a.cellsW), a, grid, s);
         return hipGetLastError();
     }
-    OVRFSR_DISPATCH_FMT(easu_go, strict, a, grid, lds, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_go, strict, a, grid, lds, s)
 }
 
 bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW)
@@ -649,7 +606,7 @@ hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a_in, 
     const bool strict = prec == PREC_FP32_STRICT;
     if (a.tileList && (strict || nTiles == 0)) return hipErrorInvalidValue; // lists are a product-build feature
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
-    OVRFSR_DISPATCH_FMT(rcas_go, strict, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, rcas_go, strict, a, grid, s)
 }
 
 } // namespace ovrfsr

@@ -43,6 +43,28 @@ hipError_t tie_audit_read(unsigned long long out[6], bool reset); // -DOVRFSR_TI
 hipError_t bounds_read_fsr(unsigned long long *out, bool reset);
 hipError_t bounds_read_nis(unsigned long long *out, bool reset);
 hipError_t bounds_selftest();
+// `return FN<in_fmt, out_fmt>(args)` of a launcher's run-time `in_fmt` / `out_fmt`: the nine pairs of RGBA8 / RGBA16F / RGBA32F, then TAIL --
+// OVRFSR_TEN_BIT_PAIRS: R10G10B10A2, only what the reference's 10-bit path needs (10-bit in -> 10-bit out, PostProcessor.cpp:63-74) plus a
+// float destination for un-quantised parity checks; OVRFSR_NO_TEN_BIT: kernels that are not built for it (fused, LDS-staged outside)
+#define OVRFSR_DISPATCH_FMT(TAIL, FN, ...)                               \
+    switch (in_fmt < 3 && out_fmt < 3 ? in_fmt * 3 + out_fmt : -1) {     \
+    case 0: return FN<FMT_RGBA8, FMT_RGBA8>(__VA_ARGS__);                \
+    case 1: return FN<FMT_RGBA8, FMT_RGBA16F>(__VA_ARGS__);              \
+    case 2: return FN<FMT_RGBA8, FMT_RGBA32F>(__VA_ARGS__);              \
+    case 3: return FN<FMT_RGBA16F, FMT_RGBA8>(__VA_ARGS__);              \
+    case 4: return FN<FMT_RGBA16F, FMT_RGBA16F>(__VA_ARGS__);            \
+    case 5: return FN<FMT_RGBA16F, FMT_RGBA32F>(__VA_ARGS__);            \
+    case 6: return FN<FMT_RGBA32F, FMT_RGBA8>(__VA_ARGS__);              \
+    case 7: return FN<FMT_RGBA32F, FMT_RGBA16F>(__VA_ARGS__);            \
+    case 8: return FN<FMT_RGBA32F, FMT_RGBA32F>(__VA_ARGS__);            \
+    default: break;                                                      \
+    }                                                                    \
+    TAIL(FN, __VA_ARGS__)                                                \
+    return hipErrorInvalidValue;
+#define OVRFSR_TEN_BIT_PAIRS(FN, ...)                                                                      \
+    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGB10A2) return FN<FMT_RGB10A2, FMT_RGB10A2>(__VA_ARGS__); \
+    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGBA32F) return FN<FMT_RGB10A2, FMT_RGBA32F>(__VA_ARGS__);
+#define OVRFSR_NO_TEN_BIT(FN, ...)
 // the kernel argument block as launched: checked builds add the dynamic LDS size of the launch
 #ifdef OVRFSR_BOUNDS
 template <typename A> static inline A with_lds(A a, size_t lds) { a.ldsBytes = (uint32_t)lds; return a; }

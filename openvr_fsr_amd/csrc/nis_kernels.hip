@@ -49,25 +49,6 @@ static hipError_t sharpen_go(bool strict, const NisArgs &a, dim3 grid, hipStream
     return hipGetLastError();
 }
 
-#define OVRFSR_DISPATCH_FMT(FN, ...)                                                                     \
-    switch (in_fmt < 3 && out_fmt < 3 ? in_fmt * 3 + out_fmt : -1) {                                                                      \
-    case 0: return FN<FMT_RGBA8, FMT_RGBA8>(__VA_ARGS__);                                                \
-    case 1: return FN<FMT_RGBA8, FMT_RGBA16F>(__VA_ARGS__);                                              \
-    case 2: return FN<FMT_RGBA8, FMT_RGBA32F>(__VA_ARGS__);                                              \
-    case 3: return FN<FMT_RGBA16F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 4: return FN<FMT_RGBA16F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 5: return FN<FMT_RGBA16F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    case 6: return FN<FMT_RGBA32F, FMT_RGBA8>(__VA_ARGS__);                                              \
-    case 7: return FN<FMT_RGBA32F, FMT_RGBA16F>(__VA_ARGS__);                                            \
-    case 8: return FN<FMT_RGBA32F, FMT_RGBA32F>(__VA_ARGS__);                                            \
-    default: break;                                                                                      \
-    }                                                                                                    \
-    /* R10G10B10A2: only what the reference's 10-bit path needs (10-bit in -> 10-bit out, PostProcessor.cpp:63-74) plus a \
-       float destination for un-quantised parity checks */                                               \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGB10A2) return FN<FMT_RGB10A2, FMT_RGB10A2>(__VA_ARGS__); \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGBA32F) return FN<FMT_RGB10A2, FMT_RGBA32F>(__VA_ARGS__); \
-    return hipErrorInvalidValue;
-
 template <int I, int O>
 static hipError_t nis_outside_go(const NisArgs &a, dim3 grid, hipStream_t s)
 {
@@ -88,7 +69,7 @@ hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a_in, uint
         return launch_outside_staged(24, in_fmt, FMT_RGBA32F, out_fmt, o, nGroups, batch, s);
     }
     const dim3 grid(nGroups, 1, batch);
-    OVRFSR_DISPATCH_FMT(nis_outside_go, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, nis_outside_go, a, grid, s)
 }
 
 hipError_t launch_nis_scaler(int prec, int in_fmt, int out_fmt, const NisArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nGroups)
@@ -99,25 +80,11 @@ hipError_t launch_nis_scaler(int prec, int in_fmt, int out_fmt, const NisArgs &a
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
     const dim3 grid(a.tileList ? nGroups : a.tilesX * a.tilesY, 1, batch);
     const size_t lds = nis_scaler_lds_bytes(a.cellsW, a.cellsH);
-    OVRFSR_DISPATCH_FMT(scaler_go, prec == PREC_FP32_STRICT, a, grid, lds, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, scaler_go, prec == PREC_FP32_STRICT, a, grid, lds, s)
 }
 
 #ifdef OVRFSR_BOUNDS
-hipError_t bounds_read_nis(unsigned long long *out, bool reset)
-{
-    unsigned long long c[ovrfsr_chk::kSlots];
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(c, HIP_SYMBOL(ovrfsr_chk::g_counts), sizeof c);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < ovrfsr_chk::kFirstRec; ++i) out[i] += c[i];
-    if (out[ovrfsr_chk::kFirstRec] == 0 && c[ovrfsr_chk::kFirstRec] != 0)
-        for (int i = ovrfsr_chk::kFirstRec; i < ovrfsr_chk::kSlots; ++i) out[i] = c[i];
-    if (reset) {
-        for (unsigned long long &v : c) v = 0;
-        e = hipMemcpyToSymbol(HIP_SYMBOL(ovrfsr_chk::g_counts), c, sizeof c);
-    }
-    return e;
-}
+hipError_t bounds_read_nis(unsigned long long *out, bool reset) { return ovrfsr_chk::read_counts(out, reset); }
 #else
 hipError_t bounds_read_nis(unsigned long long *, bool) { return hipErrorNotSupported; }
 #endif
@@ -129,7 +96,7 @@ hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &
     a.tilesXMagic = div_magic(a.tilesX);
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
     const dim3 grid(a.tilesX * a.tilesY, 1, batch);
-    OVRFSR_DISPATCH_FMT(sharpen_go, prec == PREC_FP32_STRICT, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, sharpen_go, prec == PREC_FP32_STRICT, a, grid, s)
 }
 
 } // namespace ovrfsr

@@ -22,6 +22,13 @@ uint32_t classify_mask(const uint32_t centre[4], uint32_t r2, uint32_t outW, uin
 void debug_fail_resource(int nth); // checked builds: the nth device allocation / stream / event creation from now on fails, once (postprocessor.cpp)
 #endif
 
+// a device allocation that knows its size
+struct DeviceBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+    void release();
+};
+
 class PostProcessor {
 public:
     PostProcessor(int device, const ovrfsr_config &cfg);
@@ -101,7 +108,7 @@ private:
     bool lastApplyRecorded_ = false; // the last Apply only recorded its submission (ovrfsr_pair_pending)
     bool capturing_ = false;         // the stream of the call in progress is being captured into a HIP graph: launches only, no (re)build
     ovrfsr_image pendingIn_{}, pendingOut_{};
-    void *retired_ = nullptr; // a ctx-owned output image a flushed pair_submit eye was handed in, kept across the rebuild of a size change
+    DeviceBuffer retired_;    // a ctx-owned output image a flushed pair_submit eye was handed in, kept across the rebuild of a size change
     void ResetKeeping(bool keepRetired);
     int FlushPending(hipStream_t stream);
     bool OverlapOutside(const ovrfsr_image &in) const; // does a masked pass run its outside-tile kernel on the auxiliary stream?
@@ -110,14 +117,10 @@ private:
     int nisCellsW_ = 0, nisCellsH_ = 0;
 
     // ctx-owned device buffers: upscaledTexture / sharpenedTexture, PostProcessor.h:43-45,58-59
-    void *swizzled_ = nullptr;          // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
-    size_t swizzledBytes_ = 0;
-    void *resolved_ = nullptr;          // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one (rows padded to 16 B), see ApplyPostProcess
-    size_t resolvedBytes_ = 0;
-    void *upscaled_ = nullptr;
-    size_t upscaledBytes_ = 0;
-    void *sharpened_ = nullptr;
-    size_t sharpenedBytes_ = 0;
+    DeviceBuffer swizzled_;  // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
+    DeviceBuffer resolved_;  // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one (rows padded to 16 B), see ApplyPostProcess
+    DeviceBuffer upscaled_;
+    DeviceBuffer sharpened_;
 
     // debug-mode GPU timing, PostProcessor.h:72-82: a ring of kQueryCount timestamp pairs; after every apply the OLDEST
     // slot is read back (so the wait is normally over already), durations are summed and every 500 readings the mean
@@ -138,18 +141,28 @@ private:
     void PrepareUpscalingResources();                                    // :285-383
     void PrepareSharpeningResources();                                   // :409-481
     int PrepareTileLists(uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH);
-    struct EyePass { int eye; uint32_t cnt; size_t inOff, outOff, inStride, outStride; bool split; };
-    int EyePasses(uint32_t n, int firstEye, int alternate, size_t inStride, size_t outStride, EyePass out[2]) const;
+    // one masked launch round: images first, first + step, ... (cnt of them) of the batch, all of eye `eye` when `split`
+    struct EyePass {
+        int eye; uint32_t cnt, first, step; bool split;
+        template <class Args> void Select(Args &a) const; // narrows an argument block of the whole batch (its view, its mask) to this pass
+    };
+    int EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const;
+    // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text
+    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, hipStream_t stream, const char *what, Body body);
+    int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
+    template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
+    void FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     void FillEasu(EasuArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     int PrepareNisResources();                                           // :307-310, :366-382, :432-435
     void FillNis(NisArgs &a, int firstEye, int alternate) const;
-    int EnsureBuffer(void **buf, size_t *have, size_t need);
+    int EnsureBuffer(DeviceBuffer &buf, size_t need);
+    int IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride); // the upscale stage's destination in front of a sharpening stage
     static bool RangesOverlap(const ovrfsr_image &in0, size_t inStride, const ovrfsr_image &out0, size_t outStride, uint32_t n);
     uint32_t IntermediateFormat() const;
     bool ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const;
     float TieHalfMin() const;
     int ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                         const ovrfsr_image &out, size_t outStride, hipStream_t stream, bool timerStarted = false); // :563-638
+                         const ovrfsr_image &out, size_t outStride, hipStream_t stream); // :563-638
     int ApplyUpscaling(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
                        const ovrfsr_image &out, size_t outStride, hipStream_t stream);   // :385-401
     int ApplySorted(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,

@@ -240,6 +240,13 @@ def test_refusals_leave_the_ctx_enabled(gpu):
     # a multisampled output
     out_ms = torch.zeros((107, 128, 4, 4), dtype=torch.uint8, device="cuda")
     assert call(good, _img(out_ms.view(107, 128 * 4, 4), K.format_ms(K.FORMAT_RGBA8, 4), width=128)) == 2
+    # ... of any base format, BGRA8 (itself input-only) included, and whatever its pitch: the caller's likely mistake is a single-sample
+    # pitch, and the refusal must be the header's OVRFSR_ERR_UNSUPPORTED in front of the size and pitch tests, not "bad pitch"
+    for base in (K.FORMAT_BGRA8, K.FORMAT_RGBA8, K.FORMAT_R11G11B10F):
+        for o in (_img(out, K.format_ms(base, 4)), _img(out_ms.view(107, 128 * 4, 4), K.format_ms(base, 4), width=128)):
+            assert call(good, o) == 2, (base, o.pitch_bytes)
+            want_text = b"out: R11G11B10F is an input-only format" if base == K.FORMAT_R11G11B10F else b"out: multisampled images are input-only"
+            assert lib.ovrfsr_last_error(pp._ctx) == want_text, (base, lib.ovrfsr_last_error(pp._ctx))
     # sample counts 3 and 16, an unknown bit
     for bad_fmt in (K.format_ms(K.FORMAT_RGBA8, 3), K.format_ms(K.FORMAT_RGBA8, 16), K.FORMAT_RGBA8 | 1 << 20, K.format_ms(5, 4)):
         assert call(_img(ms.view(80, 96 * 4, 4), bad_fmt, width=96)) == 2, hex(bad_fmt)
