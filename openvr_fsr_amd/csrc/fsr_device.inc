@@ -102,6 +102,29 @@ __device__ __forceinline__ float raw_max3(float a, float b, float c) { float r; 
 __device__ __forceinline__ float raw_min(float a, float b) { float r; __asm__("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float raw_max(float a, float b) { float r; __asm__("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
+#define OVRFSR_RCAS_LIMIT ((float)(0.25 - (1.0 / 16.0))) /* fsr/ffx_fsr1.h:654 */
+
+// FsrRcasF's lobe (ffx_fsr1.h:722-738) times sharp, from the per-channel extrema of the four ring taps in the BYTE domain (P = 255) --
+// one quotient per channel instead of the reference's two.  For 0 <= mn <= mx <= P:
+//     max(-mn/(4mx), (P-mx)/(4mn-4P)) = -min(mn, P-mx) / (4 min(mx, P-mn)),
+// since mn/mx <= (P-mx)/(P-mn) <=> mn + mx <= P, where both minima pick (mn, mx); otherwise both pick (P-mx, P-mn).  The extrema of
+// bytes are integers, so the selection is exact and the winning quotient is the very fp32 expression the two-quotient form evaluates
+// (v_rcp_f32 is odd and scales exactly with powers of two).  Not for the unit domain: values above 1 break 0 <= mx <= P.
+//   * The 4 of the denominator is a power of two: it moves, exactly, into the clamp limit and the sharpness factor (one multiply per
+//     thread instead of one per channel).
+//   * mn = mx in {0, P} gives 0 * rcp(0) = NaN where the two-quotient form drops its NaN against the other quotient's -1/4 ("this
+//     channel does not limit").  Here v_min3_f32 drops it, and if all three channels are NaN, v_med3_f32 answers
+//     min3(NaN, -4 LIMIT, 0) = -4 LIMIT: the same clamped lobe.
+// tests/test_gpu_rcas_identity.py compares this helper with the two-quotient form on the device, bit for bit, over every (mn, mx).
+__device__ __forceinline__ float rcas_lobe_bytes(float mnR, float mxR, float mnG, float mxG, float mnB, float mxB, float sharp)
+{
+    constexpr float P = 255.0f;
+    const float qR = raw_min(mnR, P - mxR) * __builtin_amdgcn_rcpf(raw_min(mxR, P - mnR));
+    const float qG = raw_min(mnG, P - mxG) * __builtin_amdgcn_rcpf(raw_min(mxG, P - mnG));
+    const float qB = raw_min(mnB, P - mxB) * __builtin_amdgcn_rcpf(raw_min(mxB, P - mnB));
+    return __builtin_amdgcn_fmed3f(-raw_min3(qR, qG, qB), -4.0f * OVRFSR_RCAS_LIMIT, 0.0f) * (0.25f * sharp);
+}
+
 // The same guard for RGBA16F stores (round 4 form): is a positive x, about to be rounded to half, within 2^-TIE_HALF_BITS of a
 // half SPACING of a rounding boundary?  The low 13 bits of the fp32 pattern are x's position inside its half spacing in
 // fixed point (boundary = 0x1000), whatever the binade: the band follows x's magnitude, as the re-association error it covers

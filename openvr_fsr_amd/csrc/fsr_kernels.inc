@@ -634,12 +634,16 @@ __device__ __forceinline__ void easu_resolve_fast2(OVRFSR_PTR_RC(float4) col, OV
         { const float4 c = col[base + PITCH + 2]; both(c, rA2 + cA2, rB1 + cB2); }   // A l | B h
         both(c02, rA3, rB2);                 // A n | B j
         both(c12, rA3 + cA, rB2 + cB);       // A o | B k
-        mnR = raw_min(raw_min3(c00.x, c10.x, c01.x), c11.x); mxR = raw_max(raw_max3(c00.x, c10.x, c01.x), c11.x);
-        mnG = raw_min(raw_min3(c00.y, c10.y, c01.y), c11.y); mxG = raw_max(raw_max3(c00.y, c10.y, c01.y), c11.y);
-        mnB = raw_min(raw_min3(c00.z, c10.z, c01.z), c11.z); mxB = raw_max(raw_max3(c00.z, c10.z, c01.z), c11.z);
-        nnR = raw_min(raw_min3(c01.x, c11.x, c02.x), c12.x); nxR = raw_max(raw_max3(c01.x, c11.x, c02.x), c12.x);
-        nnG = raw_min(raw_min3(c01.y, c11.y, c02.y), c12.y); nxG = raw_max(raw_max3(c01.y, c11.y, c02.y), c12.y);
-        nnB = raw_min(raw_min3(c01.z, c11.z, c02.z), c12.z); nxB = raw_max(raw_max3(c01.z, c11.z, c02.z), c12.z);
+        // the dering boxes of A (c00 c10 c01 c11) and B (c01 c11 c02 c12) share cells c01 and c11: their extrema once (18 min/max for 24)
+        const float loR = raw_min(c01.x, c11.x), hiR = raw_max(c01.x, c11.x);
+        const float loG = raw_min(c01.y, c11.y), hiG = raw_max(c01.y, c11.y);
+        const float loB = raw_min(c01.z, c11.z), hiB = raw_max(c01.z, c11.z);
+        mnR = raw_min3(c00.x, c10.x, loR); mxR = raw_max3(c00.x, c10.x, hiR);
+        mnG = raw_min3(c00.y, c10.y, loG); mxG = raw_max3(c00.y, c10.y, hiG);
+        mnB = raw_min3(c00.z, c10.z, loB); mxB = raw_max3(c00.z, c10.z, hiB);
+        nnR = raw_min3(loR, c02.x, c12.x); nxR = raw_max3(hiR, c02.x, c12.x);
+        nnG = raw_min3(loG, c02.y, c12.y); nxG = raw_max3(hiG, c02.y, c12.y);
+        nnB = raw_min3(loB, c02.z, c12.z); nxB = raw_max3(hiB, c02.z, c12.z);
     }
     const float rWA = __builtin_amdgcn_rcpf(aBW.y), rWB = __builtin_amdgcn_rcpf(bBW.y);
     aR = __builtin_amdgcn_fmed3f(aRG.x * rWA, mnR, mxR);
@@ -1115,7 +1119,6 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
 // ------------------------------------------------------------------------------------------------
 // RCAS
 // ------------------------------------------------------------------------------------------------
-#define OVRFSR_RCAS_LIMIT ((float)(0.25 - (1.0 / 16.0))) /* fsr/ffx_fsr1.h:654 */
 
 // FsrRcasF, fsr/ffx_fsr1.h:684-769, on unit-domain taps (FSR_RCAS_DENOISE undefined: the nz term is dead)
 __device__ __forceinline__ void rcas_resolve(const float4 &b, const float4 &d, const float4 &e, const float4 &f, const float4 &h,
@@ -1228,14 +1231,19 @@ __device__ __forceinline__ void rcas_resolve_bytes(const float4 &b, const float4
     const float mnR = raw_min(raw_min3(b.x, d.x, f.x), h.x), mxR = raw_max(raw_max3(b.x, d.x, f.x), h.x);
     const float mnG = raw_min(raw_min3(b.y, d.y, f.y), h.y), mxG = raw_max(raw_max3(b.y, d.y, f.y), h.y);
     const float mnB = raw_min(raw_min3(b.z, d.z, f.z), h.z), mxB = raw_max(raw_max3(b.z, d.z, f.z), h.z);
-    const float hitMinR = mnR * __builtin_amdgcn_rcpf(4.0f * mxR);
-    const float hitMinG = mnG * __builtin_amdgcn_rcpf(4.0f * mxG);
-    const float hitMinB = mnB * __builtin_amdgcn_rcpf(4.0f * mxB);
-    const float hitMaxR = (PEAK - mxR) * __builtin_amdgcn_rcpf(4.0f * mnR + -4.0f * PEAK);
-    const float hitMaxG = (PEAK - mxG) * __builtin_amdgcn_rcpf(4.0f * mnG + -4.0f * PEAK);
-    const float hitMaxB = (PEAK - mxB) * __builtin_amdgcn_rcpf(4.0f * mnB + -4.0f * PEAK);
-    const float lobeR = fmaxf(-hitMinR, hitMaxR), lobeG = fmaxf(-hitMinG, hitMaxG), lobeB = fmaxf(-hitMinB, hitMaxB);
-    const float lobe = __builtin_amdgcn_fmed3f(fmaxf(lobeR, fmaxf(lobeG, lobeB)), -OVRFSR_RCAS_LIMIT, 0.0f) * sharp;
+    float lobe;
+    if constexpr (BYTES) {
+        lobe = rcas_lobe_bytes(mnR, mxR, mnG, mxG, mnB, mxB, sharp); // one quotient per channel: exact on integers 0..255 only
+    } else {
+        const float hitMinR = mnR * __builtin_amdgcn_rcpf(4.0f * mxR);
+        const float hitMinG = mnG * __builtin_amdgcn_rcpf(4.0f * mxG);
+        const float hitMinB = mnB * __builtin_amdgcn_rcpf(4.0f * mxB);
+        const float hitMaxR = (PEAK - mxR) * __builtin_amdgcn_rcpf(4.0f * mnR + -4.0f * PEAK);
+        const float hitMaxG = (PEAK - mxG) * __builtin_amdgcn_rcpf(4.0f * mnG + -4.0f * PEAK);
+        const float hitMaxB = (PEAK - mxB) * __builtin_amdgcn_rcpf(4.0f * mnB + -4.0f * PEAK);
+        const float lobeR = fmaxf(-hitMinR, hitMaxR), lobeG = fmaxf(-hitMinG, hitMaxG), lobeB = fmaxf(-hitMinB, hitMaxB);
+        lobe = __builtin_amdgcn_fmed3f(fmaxf(lobeR, fmaxf(lobeG, lobeB)), -OVRFSR_RCAS_LIMIT, 0.0f) * sharp;
+    }
     const float rcpL = prx_med_rcp(4.0f * lobe + 1.0f);
     pr = (lobe * ((b.x + d.x) + (h.x + f.x)) + e.x) * rcpL;
     pg = (lobe * ((b.y + d.y) + (h.y + f.y)) + e.y) * rcpL;
@@ -1673,21 +1681,25 @@ __global__ __launch_bounds__(NT) OVRFSR_FUSED_OCC void fused_kernel(const ovrfsr
 #if OVRFSR_STRICT
             rcas_resolve(b, d, e, f, h, a.sharp, pr, pg, pb);
 #else
-            const float mnR = raw_min(raw_min3(b.x, d.x, f.x), h.x), mxR = raw_max(raw_max3(b.x, d.x, f.x), h.x);
-            const float mnG = raw_min(raw_min3(b.y, d.y, f.y), h.y), mxG = raw_max(raw_max3(b.y, d.y, f.y), h.y);
-            const float mnB = raw_min(raw_min3(b.z, d.z, f.z), h.z), mxB = raw_max(raw_max3(b.z, d.z, f.z), h.z);
-            const float hitMinR = mnR * __builtin_amdgcn_rcpf(4.0f * mxR);
-            const float hitMinG = mnG * __builtin_amdgcn_rcpf(4.0f * mxG);
-            const float hitMinB = mnB * __builtin_amdgcn_rcpf(4.0f * mxB);
-            const float hitMaxR = (PEAK - mxR) * __builtin_amdgcn_rcpf(4.0f * mnR + -4.0f * PEAK);
-            const float hitMaxG = (PEAK - mxG) * __builtin_amdgcn_rcpf(4.0f * mnG + -4.0f * PEAK);
-            const float hitMaxB = (PEAK - mxB) * __builtin_amdgcn_rcpf(4.0f * mnB + -4.0f * PEAK);
-            const float lobeR = fmaxf(-hitMinR, hitMaxR), lobeG = fmaxf(-hitMinG, hitMaxG), lobeB = fmaxf(-hitMinB, hitMaxB);
-            const float lobe = __builtin_amdgcn_fmed3f(fmaxf(lobeR, fmaxf(lobeG, lobeB)), -OVRFSR_RCAS_LIMIT, 0.0f) * a.sharp;
-            const float rcpL = prx_med_rcp(4.0f * lobe + 1.0f);
-            pr = (lobe * ((b.x + d.x) + (h.x + f.x)) + e.x) * rcpL;
-            pg = (lobe * ((b.y + d.y) + (h.y + f.y)) + e.y) * rcpL;
-            pb = (lobe * ((b.z + d.z) + (h.z + f.z)) + e.z) * rcpL;
+            if constexpr (mid_bytes) {
+                rcas_resolve_bytes<true>(b, d, e, f, h, a.sharp, pr, pg, pb); // the RCAS kernels' one-quotient form: one helper, so the two cannot drift
+            } else {
+                const float mnR = raw_min(raw_min3(b.x, d.x, f.x), h.x), mxR = raw_max(raw_max3(b.x, d.x, f.x), h.x);
+                const float mnG = raw_min(raw_min3(b.y, d.y, f.y), h.y), mxG = raw_max(raw_max3(b.y, d.y, f.y), h.y);
+                const float mnB = raw_min(raw_min3(b.z, d.z, f.z), h.z), mxB = raw_max(raw_max3(b.z, d.z, f.z), h.z);
+                const float hitMinR = mnR * __builtin_amdgcn_rcpf(4.0f * mxR);
+                const float hitMinG = mnG * __builtin_amdgcn_rcpf(4.0f * mxG);
+                const float hitMinB = mnB * __builtin_amdgcn_rcpf(4.0f * mxB);
+                const float hitMaxR = (PEAK - mxR) * __builtin_amdgcn_rcpf(4.0f * mnR + -4.0f * PEAK);
+                const float hitMaxG = (PEAK - mxG) * __builtin_amdgcn_rcpf(4.0f * mnG + -4.0f * PEAK);
+                const float hitMaxB = (PEAK - mxB) * __builtin_amdgcn_rcpf(4.0f * mnB + -4.0f * PEAK);
+                const float lobeR = fmaxf(-hitMinR, hitMaxR), lobeG = fmaxf(-hitMinG, hitMaxG), lobeB = fmaxf(-hitMinB, hitMaxB);
+                const float lobe = __builtin_amdgcn_fmed3f(fmaxf(lobeR, fmaxf(lobeG, lobeB)), -OVRFSR_RCAS_LIMIT, 0.0f) * a.sharp;
+                const float rcpL = prx_med_rcp(4.0f * lobe + 1.0f);
+                pr = (lobe * ((b.x + d.x) + (h.x + f.x)) + e.x) * rcpL;
+                pg = (lobe * ((b.y + d.y) + (h.y + f.y)) + e.y) * rcpL;
+                pb = (lobe * ((b.z + d.z) + (h.z + f.z)) + e.z) * rcpL;
+            }
 #endif
             pa = PEAK;
         } else {
