@@ -78,7 +78,8 @@ typedef enum ovrfsr_format {
  * pipeline: an R11G11B10F submission gives, byte for byte, what the RGBA16F image holding the same values (alpha 1.0) gives, on every
  * path and in every build -- same intermediate choices, same tolerances, same texel-value domain (no negative values exist; Inf and NaN
  * codes fall under the texel-value clause below: outside the parity contract, inside the memory-safety one).  Destinations: those of
- * an RGBA16F input (RGBA8, RGBA16F, RGBA32F); a ctx-owned output (out->data == NULL) is RGBA16F.  As an `out`, and for ovrfsr_save_ppm /
+ * an RGBA16F input (RGBA8, RGBA16F, RGBA32F); a ctx-owned output (out->data == NULL) is RGBA16F -- RGBA8, through a UNORM8 intermediate,
+ * with cfg.reference_formats = 1, which is what the reference does with such a texture.  As an `out`, and for ovrfsr_save_ppm /
  * ovrfsr_save_dds: OVRFSR_ERR_UNSUPPORTED (the float -> float11 rounding is left to the implementation by D3D, and the reference never
  * writes the format); the ctx stays enabled.  OVRFSR_FORMAT_MS(OVRFSR_FORMAT_R11G11B10F, S), S = 2, 4, 8, is accepted with the
  * multisampled layout below and the float resolve rule applied to the decoded samples (fp32 sum in sample order, times 1/S, half
@@ -240,7 +241,28 @@ typedef struct ovrfsr_config {
                                 ovrfsr_set_config / ovrfsr_destroy DROP a recorded eye and forget the learned order.  Both eyes must get their own output image:
                                 caller-owned ones, or the two ctx-owned images of this mode (a ctx-owned image handed out for a recorded
                                 eye stays valid across the rebuild a size change triggers, until the next reset)                */
-    int32_t reserved[2];
+    int32_t reference_formats; /* (was reserved[0]; same struct size, ABI version unchanged)
+                                0 = the default, THIS LIBRARY'S OWN rule (BASELINE C5, packed-half I/O): the intermediate and a ctx-owned
+                                output have the format of the pipeline's input -- an RGBA16F / R11G11B10F submission runs through a half
+                                intermediate and comes back as RGBA16F, an RGBA32F one as RGBA32F.
+                                1 = THE REFERENCE'S rule: both of its own textures are created in DetermineOutputFormat(input)
+                                (PostProcessor.cpp:63-74, 340-352, 462-475): R10G10B10A2_UNORM for a 10-bit submission, R8G8B8A8_UNORM for
+                                everything else, RGBA16F, RGBA32F and R11G11B10F included.  With quantize_intermediate = 1 the
+                                intermediate, and in any case the ctx-owned output (out->data == NULL, both ctx-owned images of
+                                pair_submit), are RGBA8 for a float submission: EASU writes a saturating UNORM8 intermediate, RCAS
+                                sharpens bytes (strict build: bit-identical to the oracle's composition; product build: <= 1 LSB, and the
+                                UNORM8 EASU store of a float source is the strict build's bit for bit -- near-tie guard with the band
+                                2^-9 byte x max(1, largest texel of the tile's footprint), audited: profiles/reference_formats.txt).
+                                A caller-owned `out` keeps selecting the final store conversion (an RGBA32F `out` still serves parity
+                                measurements); quantize_intermediate = 0 keeps its fp32 intermediate, only the ctx-owned output's format
+                                follows the rule.  For RGBA8, BGRA8 and RGB10A2 inputs the field changes nothing.  cfg.fused = 1 with
+                                the rule and a float pipeline input fails the (re)build with OVRFSR_ERR_UNSUPPORTED, like RGB10A2 (no
+                                fused kernel is built for a byte intermediate of a float source); fused = -1 takes the mask-sorted
+                                two-kernel form there.  Values other than 0 and 1: OVRFSR_ERR_INVALID_ARGUMENT.  A library older than this
+                                field ignores it (reserved was never validated): a host probes by submitting a float image with
+                                out->data == NULL and reading out->format.  The config-file parser does not set it (the reference has no
+                                such key)                                                                                        */
+    int32_t reserved[1];
 } ovrfsr_config;
 
 typedef struct ovrfsr_ctx ovrfsr_ctx; /* one per device; not thread-safe; distinct ctxs are independent */

@@ -46,7 +46,8 @@ class Config(C.Structure):
                 ("debug_mode", C.c_int32), ("render_scale", C.c_float), ("sharpness", C.c_float),
                 ("radius", C.c_float), ("proj_centre", C.c_float * 4), ("out_width", C.c_uint32),
                 ("out_height", C.c_uint32), ("precision", C.c_int32), ("quantize_intermediate", C.c_int32),
-                ("fused", C.c_int32), ("stage_mask", C.c_int32), ("pair_submit", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("fused", C.c_int32), ("stage_mask", C.c_int32), ("pair_submit", C.c_int32), ("reference_formats", C.c_int32),
+                ("reserved", C.c_int32 * 1)]
 
     @classmethod
     def default(cls, **kw):

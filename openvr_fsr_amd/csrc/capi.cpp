@@ -34,7 +34,7 @@ bool config_valid(const ovrfsr_config *cfg)
 {
     return config_ok(cfg) && (cfg->precision == OVRFSR_PRECISION_FP32 || cfg->precision == OVRFSR_PRECISION_FP32_STRICT) &&
            cfg->stage_mask >= 0 && cfg->stage_mask <= 2 && cfg->fused >= -1 && cfg->fused <= 1 && (cfg->pair_submit == 0 || cfg->pair_submit == 1) &&
-           floats_valid(cfg);
+           (cfg->reference_formats == 0 || cfg->reference_formats == 1) && floats_valid(cfg);
 }
 
 // Nothing may unwind through the extern "C" boundary (header: "nothing here throws"): host-side containers of the launch

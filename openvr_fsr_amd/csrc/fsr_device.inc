@@ -177,6 +177,23 @@ __device__ __forceinline__ bool near_tie_half3_hdr(float r, float g, float b, fl
     return (int)near_tie_half_abs(r, bp, xmin) | (int)near_tie_half_abs(g, bp, xmin) | (int)near_tie_half_abs(b, bp, xmin);
 }
 
+// The same guard for UNORM8 stores of FLOAT sources (cfg.reference_formats: the reference's R8G8B8A8_UNORM intermediate of an HDR
+// submission).  x: a unit-domain channel of the product resolve; what is stored is floor(sat(x) * 255 + 0.5), so the test runs on
+// sat(x) * 255: is it within `band` bytes of a rounding boundary k + 0.5?  band = 2^-kTieBits byte (the byte guard's) x max(1, tmax), tmax
+// the largest |channel| of the tile's staged footprint (the HDR half guard's reasoning: the re-association error follows the largest
+// tap, not the output, and 2^-9 byte = 2^-17 of the unit range is that guard's band).  Saturated channels sit at 0 or 255, half a byte
+// from the nearest boundary: they are listed only where the band reaches 0.5 byte (tmax >= 256) -- there a product value just above 1
+// can be a strict value just below 254.5 / 255, and every pixel of the tile is re-resolved in reference order.  band = 0: never (guard off).
+__device__ __forceinline__ bool near_tie_unorm8_unit(float x, float band)
+{
+    const float v = sat01(x) * 255.0f;
+    return fabsf((v - floorf(v)) - 0.5f) < band;
+}
+__device__ __forceinline__ bool near_tie_unorm8_unit3(float r, float g, float b, float band)
+{
+    return (int)near_tie_unorm8_unit(r, band) | (int)near_tie_unorm8_unit(g, band) | (int)near_tie_unorm8_unit(b, band);
+}
+
 typedef _Float16 half_t;
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));

@@ -25,11 +25,20 @@ constexpr uint32_t texel_bytes(uint32_t fmt)
 
 // What the kernels see in a submission's place once the resolve pass or the BGRA8 re-order has run (PostProcessor::ApplyPostProcess): a
 // multisampled image resolved to one sample, BGRA8 re-ordered to RGBA8 (the reference reads it through a typed view and writes R8G8B8A8,
-// PostProcessor.cpp:30-61,63-74), R11G11B10F unpacked to RGBA16F.  Also the format of the ctx-owned output (DetermineOutputFormat, :63-74).
+// PostProcessor.cpp:30-61,63-74), R11G11B10F unpacked to RGBA16F.  With cfg.reference_formats = 0 (the default: this library's own rule,
+// BASELINE C5's packed-half I/O -- NOT the reference's) it is also the format of the quantised intermediate and of the ctx-owned output.
 constexpr uint32_t pipeline_format(uint32_t fmt)
 {
     return base_format(fmt) == OVRFSR_FORMAT_BGRA8_UNORM ? (uint32_t)OVRFSR_FORMAT_RGBA8_UNORM
          : base_format(fmt) == OVRFSR_FORMAT_R11G11B10F ? (uint32_t)OVRFSR_FORMAT_RGBA16F : base_format(fmt);
+}
+
+// The reference's DetermineOutputFormat (PostProcessor.cpp:63-74), the format of BOTH textures it creates (upscaledTexture :340-352,
+// sharpenedTexture :462-475): R10G10B10A2_UNORM for a 10-bit submission, R8G8B8A8_UNORM for everything else -- RGBA16F, RGBA32F and
+// R11G11B10F included.  `fmt`: a pipeline_format value.  cfg.reference_formats = 1 selects it (header).
+constexpr uint32_t reference_output_format(uint32_t fmt)
+{
+    return fmt == OVRFSR_FORMAT_RGB10A2_UNORM ? (uint32_t)OVRFSR_FORMAT_RGB10A2_UNORM : (uint32_t)OVRFSR_FORMAT_RGBA8_UNORM;
 }
 
 // nullptr, or why an image of this format cannot be a destination

@@ -326,11 +326,14 @@ static hipError_t fused_go3(bool strict, const FusedArgs &a, dim3 grid, size_t l
     }
     return hipGetLastError();
 }
-// The intermediate has the submission's format (R8G8B8A8 -> UNORM8, RGBA16F -> half: PostProcessor::IntermediateFormat, which
-// mirrors DetermineOutputFormat, PostProcessor.cpp:63-74) or, with quantize_intermediate = 0, stays in float: those are the only
-// (input, intermediate) pairs a ctx ever asks for, so only they are instantiated (12 of the 27 format triples of the fused and
-// outside-tile kernels were dead weight in the library until round 4).
+// The intermediate has the pipeline input's format (R8G8B8A8 -> UNORM8, RGBA16F -> half: PostProcessor::IntermediateFormat with
+// cfg.reference_formats = 0, this library's own rule) or, with quantize_intermediate = 0, stays in float: those are the only (input,
+// intermediate) pairs a ctx asks the FUSED kernel for, so only they are instantiated (12 of the 27 format triples of the fused and
+// outside-tile kernels were dead weight in the library until round 4).  Under cfg.reference_formats = 1 (DetermineOutputFormat,
+// PostProcessor.cpp:63-74) a float input has a UNORM8 intermediate: a ctx then asks for (RGBA16F | RGBA32F, RGBA8) too, of the
+// outside-tile kernel only (easu_outside_go) -- the fused kernel is refused for that pair at (re)build, none is built.
 template <int I, int M> constexpr bool mid_reachable() { return M == I || M == FMT_RGBA32F; }
+template <int I, int M> constexpr bool mid_reachable_outside() { return mid_reachable<I, M>() || (M == FMT_RGBA8 && (I == FMT_RGBA16F || I == FMT_RGBA32F)); }
 
 template <int I, int O>
 static hipError_t fused_go(int mid_fmt, bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
@@ -360,6 +363,8 @@ static hipError_t easu_outside_go(int mid_fmt, const EasuArgs &a, dim3 grid, hip
     if (mid_fmt < 0) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, -1>), grid, dim3(kThreads), 0, s, a);
     else if (mid_fmt == FMT_RGBA32F) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, FMT_RGBA32F>), grid, dim3(kThreads), 0, s, a);
     else if (mid_fmt == (int)I && I != FMT_RGB10A2) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, (I == FMT_RGB10A2 ? -1 : I)>), grid, dim3(kThreads), 0, s, a);
+    else if (mid_fmt == FMT_RGBA8 && mid_reachable_outside<I, FMT_RGBA8>()) // a float source behind a UNORM8 intermediate (cfg.reference_formats)
+        hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, (mid_reachable_outside<I, FMT_RGBA8>() ? (int)FMT_RGBA8 : -1)>), grid, dim3(kThreads), 0, s, a);
     else return hipErrorInvalidValue; // not an (input, intermediate) pair a ctx produces (see mid_reachable)
     return hipGetLastError();
 }

@@ -807,7 +807,10 @@ __device__ __forceinline__ uint32_t pack_bytes_rne(float r, float g, float b)
 #ifdef OVRFSR_TIE_AUDIT
 // Audit of one product-resolved pixel (see g_ovrfsr_tie_audit in fsr_kernels.hip).  (r, g, b): the product resolve's result in the domain it is
 // stored from (bytes 0..255 for UNORM8 stores of RGBA8 input; unit domain for half stores); `listed`: the near-tie guard took the pixel.
-template <bool BYTES, bool HALF_STORE>
+// UNIT8: the UNORM8 store of a FLOAT source (unit domain, store_unit on both sides); xmin then carries the pixel's band in bytes, and the
+// distance is recorded as a FRACTION OF THAT BAND in slot [5] (the band varies with the tile: a distance in bytes would not compare) --
+// the campaign that audits such stores runs nothing else, so the slot is not shared with half spacings.
+template <bool BYTES, bool HALF_STORE, bool UNIT8 = false>
 __device__ __forceinline__ void tie_audit_px(OVRFSR_PTR_RC(float4) col, OVRFSR_PTR_RC(float4) ana, int base, int pitch, float ppx, float ppy,
                                              float r, float g, float b, bool listed, float xmin)
 {
@@ -815,7 +818,13 @@ __device__ __forceinline__ void tie_audit_px(OVRFSR_PTR_RC(float4) col, OVRFSR_P
     easu_resolve<BYTES, float4>(col, ana, base, pitch, ppx, ppy, sr, sg, sb);
     bool flip = false, small = false;
     float dist = 0.0f;
-    if constexpr (!HALF_STORE) {
+    if constexpr (UNIT8) {
+        const uint32_t pv = unit_to_unorm8(r) | (unit_to_unorm8(g) << 8) | (unit_to_unorm8(b) << 16);
+        const uint32_t sv = unit_to_unorm8(sr) | (unit_to_unorm8(sg) << 8) | (unit_to_unorm8(sb) << 16);
+        flip = pv != sv;
+        // distance between the values as stored from: sat(x) * 255, in bands
+        dist = fmaxf(fabsf(sat01(r) - sat01(sr)), fmaxf(fabsf(sat01(g) - sat01(sg)), fabsf(sat01(b) - sat01(sb)))) * 255.0f / xmin;
+    } else if constexpr (!HALF_STORE) {
         // product: v_cvt_pk_u8_f32 of the byte-domain value; strict: floor(sat(x) * 255 + 0.5)
         const uint32_t pv = pack_bytes_rne(r, g, b);
         const uint32_t sv = unit_to_unorm8(sr) | (unit_to_unorm8(sg) << 8) | (unit_to_unorm8(sb) << 16) | 0xff000000u;
@@ -839,7 +848,7 @@ __device__ __forceinline__ void tie_audit_px(OVRFSR_PTR_RC(float4) col, OVRFSR_P
     if (listed) atomicAdd(&g_ovrfsr_tie_audit[1], 1ull);
     if (flip && !listed) atomicAdd(&g_ovrfsr_tie_audit[2], 1ull);
     if (small && !listed) atomicAdd(&g_ovrfsr_tie_audit[3], 1ull);
-    atomicMax(&g_ovrfsr_tie_audit[HALF_STORE ? 5 : 4], (unsigned long long)__float_as_uint(dist)); // dist >= 0: the bit pattern orders like the value
+    atomicMax(&g_ovrfsr_tie_audit[(HALF_STORE || UNIT8) ? 5 : 4], (unsigned long long)__float_as_uint(dist)); // dist >= 0: the bit pattern orders like the value
 }
 #endif
 
@@ -885,9 +894,13 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
 
     // which stores the near-tie guard (below) covers
     constexpr bool kGuardU8 = byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8, kGuardH = OUT_FMT == ovrfsr::FMT_RGBA16F;
-    constexpr bool kGuard = kGuardU8 || kGuardH;
-    // half stores of float sources: the largest |channel| of the staged footprint (HDR tiles widen the guard's band, near_tie_half3_hdr)
-    constexpr bool kTmax = kGuardH && !byte_domain;
+    // UNORM8 stores of float sources (cfg.reference_formats): guarded in the unit domain (near_tie_unorm8_unit), and only where the host
+    // switches the guard on -- a.tieHalfMin, which this instantiation has no other use for: +inf = off (the stores of every earlier
+    // release, bit for bit), finite = on
+    constexpr bool kGuardF8 = !byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8;
+    constexpr bool kGuard = kGuardU8 || kGuardH || kGuardF8;
+    // half and UNORM8 stores of float sources: the largest |channel| of the staged footprint (HDR tiles widen the guard's band, near_tie_half3_hdr)
+    constexpr bool kTmax = (kGuardH || kGuardF8) && !byte_domain;
     __shared__ uint32_t tile_tmax;
 
     if (inside_bits != 0u) {
@@ -901,6 +914,9 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
     }
     // (workgroup-uniform: one LDS read into an SGPR; meaningful only where something was staged -- elsewhere the word is uninitialised and unused)
     [[maybe_unused]] const float tmax_v = kTmax ? __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)tile_tmax)) : 1.0f;
+    // (kGuardF8: the band in bytes, workgroup-uniform; 0 = guard off.  A band of half a byte or more -- tmax >= 256 -- lists every pixel
+    // of the tile: a wave's list holds all of its 256 pixels, and the one-lane-per-pixel pass below then resolves the whole tile in reference order)
+    [[maybe_unused]] const float band_f8 = (kGuardF8 && a.tieHalfMin < __builtin_inff()) ? (1.0f / (float)(1 << kTieBits)) * fmaxf(tmax_v, 1.0f) : 0.0f;
 
     // Near-tie guard.  The re-associated resolve differs from the reference-order one by rounding noise (<= 6.5e-4 of a
     // byte measured over 1e8 values, adversarial content included: profiles/r03_easu_err.txt); where its result lies that
@@ -966,6 +982,9 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
             const half4_t h = {(half_t)r, (half_t)g, (half_t)b, (half_t)1.0f};
             if (near_tie_half3_hdr(r, g, b, a.tieHalfMin, tmax_v)) return true;
             *OVRFSR_AT(half4_t, out + (size_t)oy * a.v.out_pitch + (size_t)ox * 8) = h;
+        } else if constexpr (kGuardF8) {
+            if (near_tie_unorm8_unit3(r, g, b, band_f8)) return true;
+            store_unit<OUT_FMT>(out, a.v.out_pitch, ox, oy, r, g, b, 1.0f);
         } else if constexpr (byte_domain) {
             const float s = 1.0f / 255.0f;
             store_unit<OUT_FMT>(out, a.v.out_pitch, ox, oy, r * s, g * s, b * s, 1.0f);
@@ -995,7 +1014,12 @@ __global__ __launch_bounds__(256) void easu_fast_kernel(const ovrfsr::EasuArgs a
         tieA = put_px(ly, r0, g0, b0);
         if (oy0 + ly + 1 < a.v.outH) tieB = put_px(ly + 1, r1, g1, b1);
 #ifdef OVRFSR_TIE_AUDIT
-        if constexpr (kGuard) {
+        if constexpr (kGuardF8) { // audited where the guard is on (off: the unguarded stores of earlier releases, no contract)
+            if (band_f8 > 0.0f) {
+                tie_audit_px<false, false, true>(col, ana, base, PITCH, ppx, riA.x, r0, g0, b0, tieA, band_f8);
+                if (oy0 + ly + 1 < a.v.outH) tie_audit_px<false, false, true>(col, ana, base + drow, PITCH, ppx, riB.x, r1, g1, b1, tieB, band_f8);
+            }
+        } else if constexpr (kGuard) {
             constexpr float us = (byte_domain && kGuardH) ? 1.0f / 255.0f : 1.0f; // put_px brings byte-domain results to the unit domain before a half store
             tie_audit_px<byte_domain, kGuardH>(col, ana, base, PITCH, ppx, riA.x, r0 * us, g0 * us, b0 * us, tieA, a.tieHalfMin);
             if (oy0 + ly + 1 < a.v.outH) tie_audit_px<byte_domain, kGuardH>(col, ana, base + drow, PITCH, ppx, riB.x, r1 * us, g1 * us, b1 * us, tieB, a.tieHalfMin);

@@ -102,15 +102,32 @@ __device__ __forceinline__ void bilinear_column4(OVRFSR_PTR_R(const uint8_t) in,
         }
     } else {
         float4 c00[4], c10[4], c01[4], c11[4];
+        // (RGBA32F texels behind a UNORM8 intermediate -- cfg.reference_formats --: two batches of 8 loads instead of one of 16; with all
+        // 48 channel registers live next to the UNORM8 round trip the kernel would pass 64 VGPRs, tests/test_reference_formats.py)
+        if constexpr (IN_FMT == ovrfsr::FMT_RGBA32F && MID_FMT == ovrfsr::FMT_RGBA8) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t ra = (uint32_t)clamp0(ty[k].i0, a.v.inH - 1) * a.v.in_pitch, rb = (uint32_t)clamp0(ty[k].i0 + 1, a.v.inH - 1) * a.v.in_pitch;
-            c00[k] = load_unit_off<IN_FMT>(in, ra + xoa); c10[k] = load_unit_off<IN_FMT>(in, ra + xob);
-            c01[k] = load_unit_off<IN_FMT>(in, rb + xoa); c11[k] = load_unit_off<IN_FMT>(in, rb + xob);
+            for (int k0 = 0; k0 < 4; k0 += 2) {
+#pragma unroll
+                for (int k = k0; k < k0 + 2; ++k) {
+                    const uint32_t ra = (uint32_t)clamp0(ty[k].i0, a.v.inH - 1) * a.v.in_pitch, rb = (uint32_t)clamp0(ty[k].i0 + 1, a.v.inH - 1) * a.v.in_pitch;
+                    c00[k] = load_unit_off<IN_FMT>(in, ra + xoa); c10[k] = load_unit_off<IN_FMT>(in, ra + xob);
+                    c01[k] = load_unit_off<IN_FMT>(in, rb + xoa); c11[k] = load_unit_off<IN_FMT>(in, rb + xob);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = k0; k < k0 + 2; ++k) finish(k, c00[k], c10[k], c01[k], c11[k]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t ra = (uint32_t)clamp0(ty[k].i0, a.v.inH - 1) * a.v.in_pitch, rb = (uint32_t)clamp0(ty[k].i0 + 1, a.v.inH - 1) * a.v.in_pitch;
+                c00[k] = load_unit_off<IN_FMT>(in, ra + xoa); c10[k] = load_unit_off<IN_FMT>(in, ra + xob);
+                c01[k] = load_unit_off<IN_FMT>(in, rb + xoa); c11[k] = load_unit_off<IN_FMT>(in, rb + xob);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) finish(k, c00[k], c10[k], c01[k], c11[k]);
         }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) finish(k, c00[k], c10[k], c01[k], c11[k]);
     }
 }
 

@@ -150,6 +150,9 @@ bool PostProcessor::OverlapOutside(const ovrfsr_image &in) const
 {
     // launch_easu_outside / launch_nis_outside take the LDS-staged kernel for RGBA8 sources when upscaling (outside_staged_ok)
     const bool staged = in.format == OVRFSR_FORMAT_RGBA8_UNORM && in.width <= outputWidth_ && in.height <= outputHeight_;
+    // cfg.reference_formats: the mask-sorted form of a float source (UNORM8 intermediate) runs in order on the caller's stream, as the
+    // RGBA8 one does -- its three launches are short, and the fork / join pair costs ~10 us per cross-queue wait
+    if (useSorted_ && in.format != OVRFSR_FORMAT_RGBA8_UNORM) return false;
     return !staged;
 }
 
@@ -234,12 +237,20 @@ int PostProcessor::EnsureBuffer(DeviceBuffer &buf, size_t need)
 
 uint32_t PostProcessor::IntermediateFormat() const
 {
-    // the reference's upscaledTexture has the output format: R8G8B8A8_UNORM (PostProcessor.cpp:348 via :63-74).
-    // Half-float pipelines (BASELINE C5) keep a half-float intermediate; quantize_intermediate=0 keeps fp32.
+    // quantize_intermediate=0 keeps fp32, whatever the format rule.
     if (!cfg_.quantize_intermediate) return OVRFSR_FORMAT_RGBA32F;
-    // a 10-bit submission keeps 10-bit resources (DetermineOutputFormat, :63-74)
-    // (inputFormat_ keeps a multisampled submission's encoding for the rebuild checks; what the pipeline sees in its place decides)
-    return pipeline_format(inputFormat_);
+    return OwnedFormat(inputFormat_);
+}
+
+// The format of the textures the ctx creates for itself -- the quantised intermediate and the ctx-owned output -- for a submission of
+// format `submitted` (a multisampled encoding included: what the pipeline sees in its place decides).
+//   cfg.reference_formats = 0 (default): the pipeline input's own format.  This library's rule, not the reference's: half-float pipelines
+//     (BASELINE C5) keep a half intermediate and come back as RGBA16F.  It agrees with the reference for RGBA8, BGRA8 and RGB10A2.
+//   cfg.reference_formats = 1: the reference's DetermineOutputFormat (PostProcessor.cpp:63-74; upscaledTexture :348, sharpenedTexture :470).
+uint32_t PostProcessor::OwnedFormat(uint32_t submitted) const
+{
+    const uint32_t f = pipeline_format(submitted);
+    return cfg_.reference_formats ? reference_output_format(f) : f;
 }
 
 // the upscale stage's destination where a sharpening stage follows: n images of the output size, tight pitch, in upscaled_
@@ -410,15 +421,22 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     // radius need no intermediate at all); unmasked ones stay two-pass (VALU-bound, the ring recompute costs 9 %)
     const bool tenBit = in.format == OVRFSR_FORMAT_RGB10A2_UNORM; // two-kernel pipeline only (header)
     if (tenBit && cfg_.fused == 1) return Fail(OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for RGB10A2 images");
-    const bool autoFused = !tenBit && cfg_.fused == -1 && tileListDev_ != nullptr && fusedCellsW_ <= 40 &&
+    // cfg.reference_formats with a float pipeline input (R11G11B10F counts as RGBA16F here): the intermediate is UNORM8, and no fused kernel is
+    // built for a byte intermediate of a float source -- two-kernel forms only, the mask-sorted one where there is a mask
+    const bool floatIn = in.format == OVRFSR_FORMAT_RGBA16F || in.format == OVRFSR_FORMAT_RGBA32F;
+    if (cfg_.reference_formats && floatIn && cfg_.fused == 1)
+        return Fail(OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for float images under reference_formats (UNORM8 intermediate of a float source)");
+    const bool byteMidOfFloat = floatIn && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
+    const bool autoFused = !tenBit && !byteMidOfFloat && cfg_.fused == -1 && tileListDev_ != nullptr && fusedCellsW_ <= 40 &&
                            fused_lds_bytes(cfg_.precision, (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) <= kFusedLdsMax;
     // auto on a masked product-build EASU+RCAS pipeline: the two-pass kernels on the tiles touching the radius, tiles
     // outside written in final form (ApplySorted); cfg.fused = 1 keeps the single fused kernel on those tiles
     // Measured: with 4-byte pixels the sorted two-pass form wins (C2 shape, radius 0.5: +13 %); with 8/16-byte
     // pixels the outside kernel dominates the frame, and the three dependent launches of the sorted form lose to the
-    // fused kernel (C5: -15 %), so those keep it.
+    // fused kernel (C5: -15 %), so those keep it.  The condition is the INTERMEDIATE's format: under cfg.reference_formats a float source
+    // has a UNORM8 intermediate too, and takes this form (RCAS on rcas_dpp_kernel's span records; profiles/reference_formats.txt).
     useSorted_ = cfg_.fused == -1 && tileListDev_ != nullptr && doUpscale_ && doSharpen_ && !cfg_.use_nis &&
-                 in.format == OVRFSR_FORMAT_RGBA8_UNORM && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
+                 (in.format == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
     if ((cfg_.fused == 1 || (autoFused && !useSorted_)) && doUpscale_ && doSharpen_ && !cfg_.use_nis) {
         const bool pitchOk = cfg_.precision == OVRFSR_PRECISION_FP32_STRICT || fusedCellsW_ <= 40;
         if (!pitchOk || fused_lds_bytes(cfg_.precision, (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) > kFusedLdsMax)
@@ -745,6 +763,11 @@ void PostProcessor::FillEasu(EasuArgs &a, const ovrfsr_image &in, size_t inStrid
     a.ringStrips = 0;
     a.rcpOutW = rcpOut_[0]; a.rcpOutH = rcpOut_[1]; a.rcpExact = rcpExact_ ? 1u : 0u;
     a.outsideCols = outsideCols_; a.outsideRows = outsideRows_[0];
+    // UNORM8 store of a float source (easu_fast_kernel<RGBA16F / RGBA32F, RGBA8>: the kernel has no half store, so the field is its guard's
+    // SWITCH): +inf = off, the stores of every earlier release; finite = on, the store is the strict build's bit for bit.  On exactly
+    // under cfg.reference_formats -- the pipeline's UNORM8 intermediate and an EASU-only RGBA8 output alike.
+    if ((in.format == OVRFSR_FORMAT_RGBA16F || in.format == OVRFSR_FORMAT_RGBA32F) && out.format == OVRFSR_FORMAT_RGBA8_UNORM)
+        a.tieHalfMin = cfg_.reference_formats ? 0.0f : INFINITY;
 }
 
 void PostProcessor::FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride,
@@ -1038,8 +1061,8 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         dst = canonical(*out);
     } else {
         dst.width = outputWidth_; dst.height = outputHeight_;
-        // DetermineOutputFormat (:63-74); an R11G11B10F submission gets what the RGBA16F image of the same values gets (header)
-        dst.format = pipeline_format(in->format);
+        // an R11G11B10F submission gets what the RGBA16F image of the same values gets (header)
+        dst.format = OwnedFormat(in->format);
         dst.pitch_bytes = dst.width * texel_bytes(dst.format);
         // (pair mode: both eyes' results are alive at once -- two ctx-owned images, left first)
         const size_t one = (size_t)dst.pitch_bytes * dst.height;

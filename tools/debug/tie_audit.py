@@ -14,7 +14,16 @@ It also records the largest |product - strict| it met (bytes of the UNORM8 domai
 Content: natural images (round 6: tests/golden/natural_*.npz, mirror-tiled), the bench's structured and uniform-random generators, 0 / 255-heavy images, and a mosaic of 8x8-texel patches of the families the
 adversarial search (tools/debug/easu_err_search.py) mutates -- two-level edges at random angles, ramps with noise, near-constant patches with
 outliers, extremes --; for the half pipelines the same content as half(b / 255 * s), s in {1, 6, 40} (unit range and HDR).
-Shapes: BASELINE C2 (x4/3), C4 (x1.3), C5 (x4/3, masked and unmasked, half), and odd ratios (x1.7, x1.11, x2)."""
+Shapes: BASELINE C2 (x4/3), C4 (x1.3), C5 (x4/3, masked and unmasked, half), and odd ratios (x1.7, x1.11, x2).
+
+    OVRFSR_LIB=$PWD/ab/audit.so python tools/debug/tie_audit.py --reference-formats [scale=1.0] [seed_offset=0]
+
+runs ONLY the campaign of cfg.reference_formats = 1 (the default campaign, whose totals tests/test_gpu_adversarial.py asserts, holds none of
+it): UNORM8 stores of FLOAT sources -- the UNORM8 intermediate of an RGBA16F / RGBA32F pipeline and the EASU-only RGBA8 output -- on unit-range
+content and every HDR kind of tests/test_gpu_formats.py::_hdr_image (the structured image scaled x2 / x6 / x40; a dark image with 2 % highlights
+at x6 / x40 / x400), masked (mask-sorted form, radius 0.5) and unmasked, at the three LDS pitches of easu_fast_kernel (28: x4/3, 32: x1.3,
+40: x1.11).  The guard's band there is 2^-9 byte x max(1, largest texel of the tile's footprint): the distance is reported as a fraction of
+the band of the pixel it was met at."""
 import ctypes
 import os
 import sys
@@ -107,7 +116,64 @@ def run(tag, inW, inH, outW, outH, content, n, seed, half_scale=None, **cfg):
     return c
 
 
+def hdr_batch(n, w, h, seed, scale, kind, dtype):
+    """tests/test_gpu_formats.py::_hdr_image on the device: the structured generator scaled as a whole, or a dark image (values <= 1) with
+    2 % of its texels at scale x U(0.5, 1)"""
+    img = bench.synth_batch(n, w, h, torch.uint8, DEV, seed).float() / 255.0
+    if kind == "scaled":
+        img = img * scale
+    else:
+        g = torch.Generator(device=DEV); g.manual_seed(seed ^ 0x9E3779B9)
+        hot = torch.rand((n, h, w, 1), generator=g, device=DEV) < 0.02
+        lit = scale * (0.5 + 0.5 * torch.rand((n, h, w, 4), generator=g, device=DEV))
+        img = torch.where(hot, lit, img)
+    img = img.to(torch.float16).to(dtype)   # (RGBA32F images hold half-representable values too: one content, two staging paths)
+    img[..., 3] = 1.0
+    return img
+
+
+def run_reference_formats(tag, inW, inH, outW, outH, n, seed, scale, kind, dtype, **cfg):
+    texs = hdr_batch(n, inW, inH, seed, scale, kind, dtype)
+    outs = torch.empty((n, outH, outW, 4), dtype=torch.uint8, device=DEV)
+    pp = A.PostProcessor(fsr_enabled=1, out_width=outW, out_height=outH, sharpness=0.9, quantize_intermediate=1, reference_formats=1, **cfg)
+    counters(reset=True)
+    pp.apply_batch(texs, outs, first_eye=A.EYE_LEFT, alternate_eyes=True)
+    torch.cuda.synchronize()
+    c = counters()
+    pp.close()
+    print("%-44s %-16s %-7s n=%3d  audited %11d  listed %10d (%6.2f %%)  FLIPS %d  max dist %.3f of the band"
+          % (tag, "%s x%g" % (kind, scale), str(dtype).split(".")[-1], n, c["audited"], c["listed"], 100.0 * c["listed"] / max(1, c["audited"]), c["flips"],
+             c["max_dist_half_spacings"]), flush=True)   # (slot [5] holds band fractions for these stores: tie_audit_px<.., UNIT8>)
+    return c
+
+
+def main_reference_formats(argv):
+    k = float(argv[0]) if argv else 1.0
+    N = lambda n: max(2, int(round(n * k)) & ~1)  # noqa: E731
+    seed = 0x5EED0000 + (int(argv[1], 0) if len(argv) > 1 else 0)
+    total = {"audited": 0, "listed": 0, "flips": 0, "dist": 0.0}
+    t0 = time.time()
+    shapes = ((1683, 1869, 2244, 2492, "x4/3 pitch 28"), (1000, 900, 1300, 1170, "x1.3 pitch 32"), (1000, 900, 1111, 1000, "x1.11 pitch 40"))
+    kinds = ((1.0, "scaled"), (2.0, "scaled"), (6.0, "scaled"), (40.0, "scaled"), (6.0, "highlights"), (40.0, "highlights"), (400.0, "highlights"))
+    i = 0
+    for (iw, ih, ow, oh, name) in shapes:
+        for (scale, kind) in kinds:
+            for (form, cfg) in (("two-pass", dict(radius=2.0)), ("mask-sorted", dict(radius=0.5)), ("EASU only", dict(radius=2.0, stage_mask=1))):
+                seed += 1000
+                i += 1
+                dtype = torch.float32 if i % 3 == 0 else torch.float16
+                c = run_reference_formats("%s %s" % (name, form), iw, ih, ow, oh, N(4), seed, scale, kind, dtype, **cfg)
+                for key in ("audited", "listed", "flips"):
+                    total[key] += c[key]
+                total["dist"] = max(total["dist"], c["max_dist_half_spacings"])
+    print("TOTAL audited %d pixels, listed %d (%.2f %%), FLIPS %d, max |product - strict| %.3f of the band (2^-9 byte x max(1, tile maximum))   [%.0f s]"
+          % (total["audited"], total["listed"], 100.0 * total["listed"] / max(1, total["audited"]), total["flips"], total["dist"], time.time() - t0))
+    sys.exit(1 if total["flips"] else 0)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--reference-formats":
+        return main_reference_formats(sys.argv[2:])
     k = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
     N = lambda n: max(2, int(round(n * k)) & ~1)  # noqa: E731
     total = {"audited": 0, "listed": 0, "flips": 0, "small_half_diffs": 0, "max_dist_bytes": 0.0, "max_dist_half_spacings": 0.0}
