@@ -138,7 +138,8 @@ typedef enum ovrfsr_format {
  * hardware keeps MORE sub-texel bits (10, 12, exact float weights), pixels outside the radius move by <= 1 LSB -- none at all at BASELINE's
  * C2 / C3 shape, whose scale is exactly 3/4 (every coordinate a multiple of 1/4), 1.9 % of the bytes at x1.3 (C4 shape) on structured and
  * natural content, 10.8 % on uniform noise; a TRUNCATING snap would move 0.6 % / 3.9 % of them by <= 2 LSB.
- * TEXEL VALUES the statements above cover (tests/test_gpu_formats.py::test_texel_value_domain): every finite value whose fp32 products do
+ * TEXEL VALUES the statements above cover (tests/test_gpu_formats.py::test_texel_value_domain; for NVScaler / NVSharpen
+ * tests/test_gpu_nis_formats.py::test_nis_texel_value_domain): every finite value whose fp32 products do
  * not overflow -- the whole RGBA16F range, negative values, denormals, RGBA32F magnitudes up to 1e18.  One thing IEEE 754 leaves open shows
  * through: min / max of a +0 and a -0.  An image holding zeros of BOTH signs can make a result that is a zero carry the other sign than the
  * oracle's (x86 and gfx950 choose differently); colour images (values >= +0) never meet it.  NaN / +-Inf texels, and magnitudes whose products

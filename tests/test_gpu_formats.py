@@ -291,34 +291,10 @@ def test_capture_dds(gpu, tmp_path, dt):
 # ------------------------------------------------------------------------------------------------
 # round 6: the DOMAIN of texel values the parity statements cover (header, "Texel values")
 # ------------------------------------------------------------------------------------------------
-def _wild(kind, w, h, rng):
-    """float32 RGBA texels far from a colour image"""
-    if kind == "half extremes, non-negative":
-        img = rng.choice(np.array([65504.0, 6e-8, 0.0, 1.0, 1e-3, 3e4, 2.5, 0.5], np.float32), size=(h, w, 4))
-    elif kind == "half extremes, negative values, no zeros":
-        img = rng.choice(np.array([65504.0, -65504.0, 6e-8, -6e-8, 1.0, 1e-3, 3e4, -2.5], np.float32), size=(h, w, 4))
-    elif kind == "zeros of both signs":
-        img = rng.choice(np.array([65504.0, 0.0, -0.0, 1.0, 1e-3, 3e4, 2.5], np.float32), size=(h, w, 4))
-    else:
-        img = rng.standard_normal((h, w, 4)).astype(np.float32) * np.float32(10.0 ** rng.uniform(-3, 3))
-        sel = rng.random((h, w, 4))
-        img[sel < 0.05] = 0.0
-        img[(sel >= 0.05) & (sel < 0.08)] = np.float32(1e-41)                      # fp32 denormals
-        if kind == "up to 1e18, denormals, zeros":
-            img *= np.float32(1e18 / float(np.abs(img).max()))
-        if kind == "NaN / Inf / 1e30":
-            img[(sel >= 0.08) & (sel < 0.10)] = np.float32(1e30)
-            img[(sel >= 0.10) & (sel < 0.12)] = np.float32(-1e30)
-            img[(sel >= 0.12) & (sel < 0.13)] = np.nan
-            img[(sel >= 0.13) & (sel < 0.14)] = np.inf
-            img[(sel >= 0.14) & (sel < 0.15)] = -np.inf
-    img = np.ascontiguousarray(img, np.float32)
-    img[..., 3] = 1.0
-    return img
+_wild = synth.wild_f32   # the families live beside the other content generators
 
 
-@pytest.mark.parametrize("kind", ["half extremes, non-negative", "half extremes, negative values, no zeros", "up to 1e18, denormals, zeros",
-                                  "zeros of both signs", "NaN / Inf / 1e30"])
+@pytest.mark.parametrize("kind", synth.WILD_KINDS)
 def test_texel_value_domain(gpu, kind):
     """What the bit-identity of the strict build covers, probed with RGBA32F texels no colour image holds (header, "Texel values"):
       * every finite value whose fp32 products do not overflow -- the extremes of the half range, negative values, fp32 denormals, 1e18: bit for bit;

@@ -7,7 +7,7 @@ import pytest
 
 import openvr_fsr_amd as A
 from oracle import oracle as O
-from tests import refgold, synth
+from tests import nis_cases, refgold, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 V = np.load(os.path.join(HERE, "golden", "nis_vectors.npz"))
@@ -108,3 +108,71 @@ def test_oracle_matches_reference_on_non_finite_texels(seed):
     c2, r2 = O.mask_constants(iw, ih, 2.0)
     blk = O.nis_block(cfg, c2, r2, 0)
     assert refgold.same_as_reference(key + "nis_sharpen", O.nis_sharpen(img, blk), lambda: O.ref_nis_sharpen(img, blk, cs, cu), nan_equal=True)
+
+
+def _pin_float(key, img, ow, oh, radius, debug, check_share):
+    """NVScaler to ow x oh and NVSharpen at the input size on one float image: the restatement against the reference's compiled code"""
+    ih, iw = img.shape[:2]
+    cs, cu = refgold.ref_nis_coefs()
+    ok, cfg = refgold.ref_nis_scaler_config(0.6, iw, ih, ow, oh)
+    assert ok
+    centre, rad = O.mask_constants(ow, oh, radius, nis_cases.PROJ, True, 1)
+    blk = O.nis_block(cfg, centre, rad, debug)
+    up = O.nis_upscale(img, ow, oh, blk, cs, cu)
+    assert not np.isnan(up).any()
+    if check_share:
+        nis_cases.assert_informative(up, key + "nis_upscale")
+    assert refgold.same_as_reference(key + "nis_upscale", up, lambda: O.ref_nis_upscale(img, ow, oh, blk, cs, cu))
+    ok, cfg = refgold.ref_nis_scaler_config(0.6, iw, ih, iw, ih)
+    assert ok
+    centre, rad = O.mask_constants(iw, ih, radius, nis_cases.PROJ, True, 1)
+    blk = O.nis_block(cfg, centre, rad, debug)
+    sh = O.nis_sharpen(img, blk)
+    assert not np.isnan(sh).any()
+    if check_share:
+        nis_cases.assert_informative(sh, key + "nis_sharpen")
+    assert refgold.same_as_reference(key + "nis_sharpen", sh, lambda: O.ref_nis_sharpen(img, blk, cs, cu))
+
+
+@pytest.mark.parametrize("radius,debug", [(2.0, 0), (0.5, 1)])
+@pytest.mark.parametrize("iw,ih,ow,oh", nis_cases.SHAPES)
+@pytest.mark.parametrize("kind", list(nis_cases.KINDS))
+def test_nis_oracle_matches_reference_on_float_content(kind, iw, ih, ow, oh, radius, debug):
+    """Finite texels outside the unit range -- highlights tens of times their neighbours, negative values -- through NVScaler and NVSharpen:
+    where the [0, 1] clamp of the `unorm` store, GetEdgeMap's thresholds and the USM limit see something colour content never shows them.
+    The images are the ones tests/test_gpu_nis_formats.py submits as RGBA16F / RGBA32F, so the yardstick of those GPU comparisons is itself
+    pinned to the reference here.  At least a quarter of the oracle's colour values must lie strictly inside (0, 1): a clamped value says
+    nothing about the arithmetic in front of the clamp."""
+    img = nis_cases.image(kind, iw, ih)
+    _pin_float("nis_float/%s/%dx%d-%dx%d/r%gd%d/" % (kind, iw, ih, ow, oh, radius, debug), img, ow, oh, radius, debug, True)
+
+
+@pytest.mark.parametrize("kind", synth.WILD_FINITE)
+def test_nis_oracle_matches_reference_on_wild_finite_texels(kind):
+    """The finite families of tests/test_gpu_formats.py::test_texel_value_domain (half extremes, negative values, fp32 denormals, 1e18, zeros
+    of both signs): nearly every output is clamped, so this guards the clamp and sign decisions of the restatement and little else."""
+    iw, ih, ow, oh = 61, 47, 80, 63
+    img = synth.wild_f32(kind, iw, ih, np.random.default_rng(50))
+    _pin_float("nis_wild/%s/" % kind, img, ow, oh, 2.0, 0, False)
+
+
+@pytest.mark.parametrize("w,h", [(128, 107), (83, 83), (96, 40)])
+def test_flat_rectangle_reaches_the_no_edge_shortcut(w, h):
+    """The condition tests/test_gpu_nis_formats.py::test_nvsharpen_float_source rests on, checked on the oracle's side (reference tables and
+    constant block: no product library involved): inside synth.FLAT_RECT, away from its border, NVSharpen's output IS the input clamped to
+    [0, 1] (no edge in the 3 x 3 map of a flat 5 x 5 neighbourhood, so no USM term) -- over whole aligned 32 x 2 spans, which is what a wave
+    of the product build needs to take its no-edge shortcut.  The "signed" rectangle holds a value below 0 and one above 1: the shortcut's
+    clamp has something to do."""
+    rx, ry, rw, rh = synth.FLAT_RECT
+    assert rx == 0 and rw >= 66 and ry % 2 == 0 and rh >= 6 and w >= rw and h >= ry + rh
+    span = (slice(ry + 2, ry + rh - 2), slice(0, 64))      # columns 0..63 read columns 0..65, these rows read rows ry .. ry + rh - 1
+    ok, cfg = refgold.ref_nis_scaler_config(0.75, w, h, w, h)
+    assert ok
+    centre, rad = O.mask_constants(w, h, 2.0)
+    blk = O.nis_block(cfg, centre, rad, 0)
+    for kind in nis_cases.KINDS:
+        img = nis_cases.image(kind, w, h)
+        flat = img[span][..., :3].reshape(-1, 3)
+        assert len(np.unique(flat, axis=0)) == 1
+        assert ((flat.min() < 0) and (flat.max() > 1)) == (kind == "signed")
+        assert same_bits(O.nis_sharpen(img, blk)[span], np.clip(img[span], np.float32(0), np.float32(1))), kind
