@@ -150,10 +150,22 @@ typedef enum ovrfsr_format {
  * OVRFSR_ERR_INVALID_ARGUMENT by ovrfsr_create / ovrfsr_set_config): on gfx950 v_pk_*_f16 issues at the rate of
  * v_pk_*_f32 (profiles/r02_valu_issue_rates.txt), the fp32 kernels already process two taps per packed instruction, and
  * half accumulation of 12 taps misses the 1e-3 tolerance (measured: 3.9e-3, profiles/r03_half_acc.txt) -- the "fp16" of BASELINE configs C2/C3/C5 is served by fp32
- * arithmetic with RGBA16F images and a half intermediate where the config asks for packed-half I/O. */
+ * arithmetic with RGBA16F images and a half intermediate where the config asks for packed-half I/O.
+ *   FP32_EXACT   exact stores.  Arithmetic, kernels, tile lists, launch forms and tolerances are FP32's; in addition every UNORM8 byte the
+ *                pipeline stores is the STRICT build's.  EASU's bytes are that already (above); here RCAS gets the same kind of guard on the
+ *                final byte: a pixel with a channel within 2^-11 byte of a rounding boundary is evaluated a second time in the reference's
+ *                operator order and stored with the reference's rounding (profiles/exact_stores.txt; audited like the
+ *                EASU guard).  Covered: every pipeline whose RCAS reads an RGBA8 intermediate or input and writes RGBA8 -- unmasked and
+ *                masked EASU+RCAS, RCAS-only, shared textures, batches, pair_submit, BGRA8 and multisampled RGBA8 submissions, float /
+ *                R11G11B10F submissions under reference_formats = 1; EASU-only passes and pixels outside the radius go through as in FP32.
+ *                Refused at (re)build with OVRFSR_ERR_UNSUPPORTED (ctx disabled until ovrfsr_reset, the caller's image untouched): use_nis,
+ *                fused = 1, quantize_intermediate = 0 in front of RCAS, and an RCAS whose source or destination is not RGBA8 (half / float /
+ *                RGB10A2 intermediates, inputs or `out` images).  Added without an ABI version change: a host probes with ovrfsr_create and
+ *                precision = 3, which a library from before this value answers with OVRFSR_ERR_INVALID_ARGUMENT. */
 typedef enum ovrfsr_precision {
     OVRFSR_PRECISION_FP32 = 0,
-    OVRFSR_PRECISION_FP32_STRICT = 2
+    OVRFSR_PRECISION_FP32_STRICT = 2,
+    OVRFSR_PRECISION_FP32_EXACT = 3
 } ovrfsr_precision;
 
 /* Stands in for vr::Texture_t{handle,eType,eColorSpace} (headers/openvr.h:177-182) plus the

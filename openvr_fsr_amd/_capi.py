@@ -18,6 +18,7 @@ def format_ms(fmt, samples):
 
 
 PRECISION_FP32, PRECISION_FP32_STRICT = 0, 2
+PRECISION_FP32_EXACT = 3  # FP32's arithmetic; every UNORM8 byte stored is the strict build's (header, ovrfsr_precision)
 EYE_LEFT, EYE_RIGHT = 0, 1
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "HIP", 4: "NO_DEVICE", 5: "DISABLED", 6: "OUT_OF_MEMORY"}

@@ -32,7 +32,7 @@ bool floats_valid(const ovrfsr_config *cfg)
 }
 bool config_valid(const ovrfsr_config *cfg)
 {
-    return config_ok(cfg) && (cfg->precision == OVRFSR_PRECISION_FP32 || cfg->precision == OVRFSR_PRECISION_FP32_STRICT) &&
+    return config_ok(cfg) && (cfg->precision == OVRFSR_PRECISION_FP32 || cfg->precision == OVRFSR_PRECISION_FP32_STRICT || cfg->precision == OVRFSR_PRECISION_FP32_EXACT) &&
            cfg->stage_mask >= 0 && cfg->stage_mask <= 2 && cfg->fused >= -1 && cfg->fused <= 1 && (cfg->pair_submit == 0 || cfg->pair_submit == 1) &&
            (cfg->reference_formats == 0 || cfg->reference_formats == 1) && floats_valid(cfg);
 }
@@ -64,6 +64,12 @@ OVRFSR_API uint32_t ovrfsr_abi_version(void) { return OVRFSR_ABI_VERSION; }
 OVRFSR_API int ovrfsr_debug_tie_audit(unsigned long long counts[6], int reset)
 {
     return ovrfsr::tie_audit_read(counts, reset != 0) == hipSuccess ? OVRFSR_OK : OVRFSR_ERR_HIP;
+}
+// the exact-stores RCAS instances (OVRFSR_PRECISION_FP32_EXACT): {audited, listed, flips, max |product - reference-order| in bytes (fp32 bits),
+// K of the band 2^-K byte the kernels were built with} -- g_ovrfsr_tie_audit_rcas in fsr_kernels.hip.  tools/debug/tie_audit.py --rcas drives it.
+OVRFSR_API int ovrfsr_debug_tie_audit_rcas(unsigned long long counts[5], int reset)
+{
+    return ovrfsr::tie_audit_read_rcas(counts, reset != 0) == hipSuccess ? OVRFSR_OK : OVRFSR_ERR_HIP;
 }
 #endif
 

@@ -85,9 +85,11 @@ __device__ __forceinline__ uint32_t unit_to_unorm10(float x) { return (uint32_t)
 // reference-order evaluation by at most 6.5e-4 byte (measured over 1e8 values incl. uniform-random and 0/255-only
 // content, profiles/r03_easu_err.txt; none above 2^-10 = 9.8e-4); the default band, 2^-9 = 1.95e-3, is 3 times that.
 constexpr int kTieBits = 9;
+// (K: the band's bit count -- kTieBits for EASU stores, kRcasTieBits for the exact-stores RCAS instances.  v + bias is rounded to 2^-15, so
+// the band's edges sit within 2^-16 byte of where the comment puts them: 1.6 % of the narrowest band accepted)
+template <int K = kTieBits>
 __device__ __forceinline__ bool near_tie_byte(float v)
 {
-    constexpr int K = kTieBits;
     static_assert(K >= 3 && K <= 12, "band half-width 2^-K byte");
     constexpr float bias = 256.0f + 1.0f / (float)(1 << K);
     constexpr uint32_t mask = ((1u << (K - 1)) - 1u) << (16 - K);

@@ -17,6 +17,11 @@
 //   [3] unlisted pixels whose half store differs in a channel BELOW xmin (outside the guard's contract: a flipped half-ulp there stays under 1e-3)
 //   [4] max |product - strict| over all audited channels, fp32 bit pattern: bytes (UNORM8 stores) ...  [5] ... or half spacings (half stores)
 __device__ unsigned long long g_ovrfsr_tie_audit[6];
+// The exact-stores RCAS instances (rcas_exact_bytes): every stored pixel evaluated in reference order as well.
+//   [0] pixels audited   [1] pixels the guard listed (stored from the reference-order evaluation)
+//   [2] FLIPS: unlisted pixels whose product bytes differ from the reference-order bytes -- the mode's claim is [2] == 0
+//   [3] max |product - reference-order| over all audited channels, in bytes, fp32 bit pattern: what the band is derived from
+__device__ unsigned long long g_ovrfsr_tie_audit_rcas[4];
 #endif
 
 namespace ovrfsr_fast {
@@ -235,8 +240,17 @@ static hipError_t easu_go(bool strict, const EasuArgs &a, dim3 grid, size_t lds,
     else easu_fast_go<I, O, false>(pitch, a, grid, s);
     return hipGetLastError();
 }
+// rcas_dpp_kernel's height for an unmasked launch of `batch` images (see rcas_go): true = the 16-row form
+static bool rcas_dpp_small(const RcasArgs &a, uint32_t batch)
+{
+    const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
+    const uint64_t wgs = (uint64_t)tx * ty * batch;
+    const uint64_t full = (wgs + kRcasResident - 1) / kRcasResident, half = (2 * wgs + kRcasResident - 1) / kRcasResident;
+    return wgs < 16 * kRcasResident && 103 * half < 200 * full;
+}
+
 template <int I, int O>
-static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t s)
+static hipError_t rcas_go(bool strict, bool exact, const RcasArgs &a, dim3 grid, hipStream_t s)
 {
 #ifdef OVRFSR_RCAS_NO_DPP /* measurement build: the per-lane-loads kernel only (reference side of tests/test_gpu_parity.py's DPP equality test) */
     constexpr bool dpp = false;
@@ -246,6 +260,26 @@ static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t
     const bool unmasked = !a.tileList && a.m.mode[0] == MASK_ALL_INSIDE && a.m.mode[1] == MASK_ALL_INSIDE;
     if (strict) {
         hipLaunchKernelGGL((ovrfsr_strict::rcas_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
+    } else if (exact) {
+        // exact stores: the same three forms, chosen by the same rules, on the guarded RGBA8 -> RGBA8 instances; no other pair has any
+        if constexpr (I == FMT_RGBA8 && O == FMT_RGBA8) {
+            if (unmasked) {
+                const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW;
+                if (rcas_dpp_small(a, grid.z)) {
+                    const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
+                    hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<false, 16>), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
+                } else {
+                    const uint32_t ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
+                    hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<false, kRcasDppTileH>), dim3(tx * ty, 1, grid.z), dim3(kThreads), 0, s, a);
+                }
+            } else if (a.tileList && a.spanRec && a.nSpans) {
+                hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<true, kRcasDppTileH>), dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
+            } else {
+                hipLaunchKernelGGL(ovrfsr_fast::rcas_direct_exact_kernel, grid, dim3(kThreads), 0, s, a);
+            }
+        } else {
+            return hipErrorInvalidValue;
+        }
     } else if constexpr (I == FMT_RGBA8 && O != FMT_RGB10A2) {
         if (dpp && unmasked) {
             const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
@@ -253,10 +287,7 @@ static hipError_t rcas_go(bool strict, const RcasArgs &a, dim3 grid, hipStream_t
             // half-height workgroups run ceil(2r) rounds of half the length (3 % more work per pixel).  One C2 eye image: r = 1.41,
             // 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us, profiles/r05_frame.txt); a batch: no difference, the
             // 8-row form wins
-            const uint64_t wgs = (uint64_t)tx * ty * grid.z;
-            const uint64_t full = (wgs + kRcasResident - 1) / kRcasResident, half = (2 * wgs + kRcasResident - 1) / kRcasResident;
-            const bool small = wgs < 16 * kRcasResident && 103 * half < 200 * full;
-            if (small) {
+            if (rcas_dpp_small(a, grid.z)) {
                 const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
                 hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_kernel<O, false, 16>), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
             } else {
@@ -578,6 +609,24 @@ hipError_t tie_audit_read(unsigned long long out[6], bool reset)
 #endif
 }
 
+// the exact-stores RCAS instances' counters (g_ovrfsr_tie_audit_rcas), same rules
+hipError_t tie_audit_read_rcas(unsigned long long out[5], bool reset)
+{
+#ifdef OVRFSR_TIE_AUDIT
+    out[4] = (unsigned long long)ovrfsr_fast::kRcasTieBits; // the band the listed count belongs to: 2^-out[4] byte
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ovrfsr_tie_audit_rcas), 4 * sizeof(unsigned long long));
+    if (e == hipSuccess && reset) {
+        const unsigned long long z[4] = {0, 0, 0, 0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ovrfsr_tie_audit_rcas), z, sizeof z);
+    }
+    return e;
+#else
+    (void)out; (void)reset;
+    return hipErrorNotSupported;
+#endif
+}
+
 hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)
 {
     launch_fresh();
@@ -607,11 +656,11 @@ hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a_in, 
     RcasArgs a = a_in;
     a.tilesXMagic = div_magic(a.tilesX);
     a.dppTilesXMagic = div_magic((uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW);
-    if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
-    const bool strict = prec == PREC_FP32_STRICT;
+    if (prec != PREC_FP32 && prec != PREC_FP32_STRICT && prec != PREC_FP32_EXACT) return hipErrorInvalidValue;
+    const bool strict = prec == PREC_FP32_STRICT, exact = prec == PREC_FP32_EXACT;
     if (a.tileList && (strict || nTiles == 0)) return hipErrorInvalidValue; // lists are a product-build feature
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
-    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, rcas_go, strict, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, rcas_go, strict, exact, a, grid, s)
 }
 
 } // namespace ovrfsr

@@ -1274,7 +1274,85 @@ __device__ __forceinline__ void rcas_resolve_bytes(const float4 &b, const float4
     pb = (lobe * ((b.z + d.z) + (h.z + f.z)) + e.z) * rcpL;
 }
 
-template <int IN_FMT, int OUT_FMT, bool CHECKED>
+// ------------------------------------------------------------------------------------------------
+// Exact stores (OVRFSR_PRECISION_FP32_EXACT): the RGBA8 -> RGBA8 instances of the two kernels below with a near-tie guard on the FINAL
+// byte, as easu_fast_kernel has one on the intermediate byte.  The product arithmetic above (one quotient per channel, v_rcp_f32, contracted
+// sums, the byte domain, RNE pack) differs from the reference-order evaluation by 1.4e-4 byte at most (measured); a pixel with a channel within
+// 2^-kRcasTieBits byte of a rounding boundary k + 1/2 is evaluated a second time exactly as ovrfsr_strict::rcas_kernel evaluates it and
+// stored through unit_to_unorm8 (floor(x * 255 + 1/2): exact ties, which RNE rounds the other way half of the time, are inside the band).
+// Every other pixel keeps the product value, whose byte is then the strict build's.  The band and the measurement behind it:
+// profiles/exact_stores.txt (audit build, tools/debug/tie_audit.py --rcas).
+//   Shape: a per-lane branch.  The taps of the pixel are live in registers where the test runs, and the kernels have no LDS to compact a
+// list through.  0.3 % of the pixels of uniform-random content are listed, so one wave-row in six runs the second evaluation for all 64
+// lanes: the guarded RCAS launch takes 14.0 instead of 10.2 us per eye at C2's size, a C2 step 8.5 % more (profiles/exact_stores.txt).
+// rcas_dpp_kernel's neighbour-lane moves sit in front of the branch, where every lane is active.
+// ------------------------------------------------------------------------------------------------
+// Measured (audit build, tools/debug/tie_audit.py --rcas 1.0: 1.96e9 pixels, structured / uniform-random / natural / tie-rich content, sharpness
+// 0 .. 1, every kernel form): largest |product - reference-order| 1.373e-4 byte; 3 x that = 4.12e-4 <= 2^-11 = 4.88e-4 byte.
+constexpr int kRcasTieBits = 11;
+// FsrRcasF in the reference's operator order on the byte taps of an RGBA8 source: what ovrfsr_strict::rcas_kernel computes (rcas_resolve
+// with OVRFSR_STRICT's rcp_f, behind load_unit), restated here because this namespace's helpers are contracted: b/255 decode, both
+// quotients per channel, unit domain, IEEE division, every operator rounded on its own.  Unit-domain result.
+__device__ __forceinline__ void rcas_resolve_ref(const float4 &bB, const float4 &dB, const float4 &eB, const float4 &fB, const float4 &hB,
+                                                 float sharp, float &pr, float &pg, float &pb)
+{
+#pragma clang fp contract(off)
+    const float bx = unorm8_to_unit(bB.x), by = unorm8_to_unit(bB.y), bz = unorm8_to_unit(bB.z);
+    const float dx = unorm8_to_unit(dB.x), dy = unorm8_to_unit(dB.y), dz = unorm8_to_unit(dB.z);
+    const float ex = unorm8_to_unit(eB.x), ey = unorm8_to_unit(eB.y), ez = unorm8_to_unit(eB.z);
+    const float fx = unorm8_to_unit(fB.x), fy = unorm8_to_unit(fB.y), fz = unorm8_to_unit(fB.z);
+    const float hx = unorm8_to_unit(hB.x), hy = unorm8_to_unit(hB.y), hz = unorm8_to_unit(hB.z);
+    const float mn4R = fminf(fminf(bx, fminf(dx, fx)), hx), mx4R = fmaxf(fmaxf(bx, fmaxf(dx, fx)), hx);
+    const float mn4G = fminf(fminf(by, fminf(dy, fy)), hy), mx4G = fmaxf(fmaxf(by, fmaxf(dy, fy)), hy);
+    const float mn4B = fminf(fminf(bz, fminf(dz, fz)), hz), mx4B = fmaxf(fmaxf(bz, fmaxf(dz, fz)), hz);
+    const float hitMinR = mn4R * (1.0f / (4.0f * mx4R)), hitMinG = mn4G * (1.0f / (4.0f * mx4G)), hitMinB = mn4B * (1.0f / (4.0f * mx4B));
+    const float hitMaxR = (1.0f - mx4R) * (1.0f / (4.0f * mn4R + -4.0f));
+    const float hitMaxG = (1.0f - mx4G) * (1.0f / (4.0f * mn4G + -4.0f));
+    const float hitMaxB = (1.0f - mx4B) * (1.0f / (4.0f * mn4B + -4.0f));
+    const float lobeR = fmaxf(-hitMinR, hitMaxR), lobeG = fmaxf(-hitMinG, hitMaxG), lobeB = fmaxf(-hitMinB, hitMaxB);
+    const float lobe = fmaxf(-OVRFSR_RCAS_LIMIT, fminf(fmaxf(lobeR, fmaxf(lobeG, lobeB)), 0.0f)) * sharp;
+    const float ra = 4.0f * lobe + 1.0f;
+    const float rb = __uint_as_float(0x7ef19fffu - __float_as_uint(ra)); // prx_med_rcp, unfused
+    const float rcpL = rb * (-rb * ra + 2.0f);
+    pr = (lobe * bx + lobe * dx + lobe * hx + lobe * fx + ex) * rcpL;
+    pg = (lobe * by + lobe * dy + lobe * hy + lobe * fy + ey) * rcpL;
+    pb = (lobe * bz + lobe * dz + lobe * hz + lobe * fz + ez) * rcpL;
+    __asm__ volatile("" : "+v"(pr), "+v"(pg), "+v"(pb)); // round to fp32 here: nothing of the store folds into the products (store_unit)
+}
+
+// The RGBA8 word an exact-stores instance writes for a pixel whose product resolve gave (pr, pg, pb) in bytes.  `counted` (audit build):
+// the pixel is stored, so it counts.
+__device__ __forceinline__ uint32_t rcas_exact_bytes(const float4 &b, const float4 &d, const float4 &e, const float4 &f, const float4 &h,
+                                                     float sharp, float pr, float pg, float pb, [[maybe_unused]] bool counted)
+{
+    uint32_t v = pack_bytes_rne(pr, pg, pb);
+    const bool tie = (int)near_tie_byte<kRcasTieBits>(pr) | (int)near_tie_byte<kRcasTieBits>(pg) | (int)near_tie_byte<kRcasTieBits>(pb);
+#ifdef OVRFSR_TIE_AUDIT
+    // audit build: every stored pixel in reference order; counters g_ovrfsr_tie_audit_rcas (fsr_kernels.hip)
+    float sr, sg, sb;
+    rcas_resolve_ref(b, d, e, f, h, sharp, sr, sg, sb);
+    const uint32_t sv = unit_to_unorm8(sr) | (unit_to_unorm8(sg) << 8) | (unit_to_unorm8(sb) << 16) | 0xff000000u;
+    if (counted) {
+        // the distance between the values the two stores round: the product's bytes clamped as its pack clamps them, sat(x) * 255 of the reference
+        auto clampb = [](float x) { return fminf(fmaxf(x, 0.0f), 255.0f); };
+        const float dist = fmaxf(fabsf(clampb(pr) - sat01(sr) * 255.0f), fmaxf(fabsf(clampb(pg) - sat01(sg) * 255.0f), fabsf(clampb(pb) - sat01(sb) * 255.0f)));
+        atomicAdd(&g_ovrfsr_tie_audit_rcas[0], 1ull);
+        if (tie) atomicAdd(&g_ovrfsr_tie_audit_rcas[1], 1ull);
+        if (!tie && v != sv) atomicAdd(&g_ovrfsr_tie_audit_rcas[2], 1ull);
+        atomicMax(&g_ovrfsr_tie_audit_rcas[3], (unsigned long long)__float_as_uint(dist));
+    }
+    if (tie) v = sv;
+#else
+    if (tie) {
+        float sr, sg, sb;
+        rcas_resolve_ref(b, d, e, f, h, sharp, sr, sg, sb);
+        v = unit_to_unorm8(sr) | (unit_to_unorm8(sg) << 8) | (unit_to_unorm8(sb) << 16) | 0xff000000u;
+    }
+#endif
+    return v;
+}
+
+template <int IN_FMT, int OUT_FMT, bool CHECKED, bool EXACT = false>
 __device__ __forceinline__ void rcas_column4(OVRFSR_PTR_R(const uint8_t) in, OVRFSR_PTR_R(uint8_t) out, const ovrfsr::RcasArgs &a,
                                              int ox, int oy, int W, int H)
 {
@@ -1307,7 +1385,10 @@ __device__ __forceinline__ void rcas_column4(OVRFSR_PTR_R(const uint8_t) in, OVR
         if (CHECKED && oy + i >= H) break;
         float pr, pg, pb;
         rcas_resolve_bytes<byte_domain>(c[i], l[i], c[i + 1], r[i], c[i + 2], a.sharp, pr, pg, pb);
-        if constexpr (byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8) {
+        if constexpr (byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8 && EXACT) {
+            *OVRFSR_AT(uint32_t, out + (size_t)(oy + i) * a.v.out_pitch + (size_t)ox * 4) =
+                rcas_exact_bytes(c[i], l[i], c[i + 1], r[i], c[i + 2], a.sharp, pr, pg, pb, true);
+        } else if constexpr (byte_domain && OUT_FMT == ovrfsr::FMT_RGBA8) {
             *OVRFSR_AT(uint32_t, out + (size_t)(oy + i) * a.v.out_pitch + (size_t)ox * 4) = pack_bytes_rne(pr, pg, pb);
         } else if constexpr (byte_domain) {
             const float s = 1.0f / 255.0f;
@@ -1318,8 +1399,8 @@ __device__ __forceinline__ void rcas_column4(OVRFSR_PTR_R(const uint8_t) in, OVR
     }
 }
 
-template <int IN_FMT, int OUT_FMT>
-__global__ __launch_bounds__(256) void rcas_direct_kernel(const ovrfsr::RcasArgs a)
+template <int IN_FMT, int OUT_FMT, bool EXACT>
+__device__ __forceinline__ void rcas_direct_body(const ovrfsr::RcasArgs a)
 {
     const uint32_t img_i = blockIdx.z;
     const uint32_t eye = (a.m.first_eye ^ (img_i & a.m.alternate)) & 1u;
@@ -1336,8 +1417,8 @@ __global__ __launch_bounds__(256) void rcas_direct_kernel(const ovrfsr::RcasArgs
     if (inside) {
         // wave-uniform: does any tap of this 32x32 tile fall outside the image?
         const bool border = tileX == 0 || tileY == 0 || (int)(tileX + 1) * ovrfsr::kTileW + 1 > W || (int)(tileY + 1) * ovrfsr::kTileH + 1 > H;
-        if (border) rcas_column4<IN_FMT, OUT_FMT, true>(in, out, a, ox, oy, W, H);
-        else rcas_column4<IN_FMT, OUT_FMT, false>(in, out, a, ox, oy, W, H);
+        if (border) rcas_column4<IN_FMT, OUT_FMT, true, EXACT>(in, out, a, ox, oy, W, H);
+        else rcas_column4<IN_FMT, OUT_FMT, false, EXACT>(in, out, a, ox, oy, W, H);
     } else {
         const float dbg = (float)a.debug;
         const float mulG = 1.0f - dbg * 0.3f;
@@ -1347,6 +1428,10 @@ __global__ __launch_bounds__(256) void rcas_direct_kernel(const ovrfsr::RcasArgs
         }
     }
 }
+template <int IN_FMT, int OUT_FMT>
+__global__ __launch_bounds__(256) void rcas_direct_kernel(const ovrfsr::RcasArgs a) { rcas_direct_body<IN_FMT, OUT_FMT, false>(a); }
+// exact stores: RGBA8 -> RGBA8 only (the copy / tint outside the radius is the reference's evaluation already)
+__global__ __launch_bounds__(256) void rcas_direct_exact_kernel(const ovrfsr::RcasArgs a) { rcas_direct_body<ovrfsr::FMT_RGBA8, ovrfsr::FMT_RGBA8, true>(a); }
 // ------------------------------------------------------------------------------------------------
 // RCAS, product build, unmasked RGBA8 source: neighbour reuse across lanes (north_star: "wave64 shuffles for neighbour
 // reuse").  FsrRcasF's side taps d and f (ffx_fsr1.h:698-707) are the centre taps e of the pixels to the left and right,
@@ -1375,81 +1460,22 @@ __device__ __forceinline__ float dpp_from_right(float v) { return __int_as_float
 // TH (round 5): rows per workgroup, 4 waves x TH / 4 rows per lane.  32 for batches; a SMALL launch -- one eye image per call, the
 // reference's own call pattern -- is 2 886 workgroups of TH = 32 on 2 048 resident slots: 1.41 rounds, the second one 41 % full.  With
 // TH = 16 the same image is 2.8 rounds of half the length (launch_rcas picks the height from the grid size: profiles/r05_frame.txt).
+// The body is fsr_rcas_dpp.inc, included as text by both kernels: the exact-stores instances add a template flag's worth of code, and a
+// kernel's name carries its template arguments -- a flag on rcas_dpp_kernel itself would rename every shipped instance
+// (profiles/r06_isa_fingerprint_r06.json), and a shared __device__ body, though always inlined, is scheduled differently.
 template <int OUT_FMT, bool SPANS = false, int TH = ovrfsr::kRcasDppTileH>
 __global__ __launch_bounds__(256) void rcas_dpp_kernel(const ovrfsr::RcasArgs a)
 {
-    constexpr int TW = ovrfsr::kRcasDppTileW, R = TH / 4; // 62 stored columns per wave, 4 waves x R rows
-    static_assert(!SPANS || TH == ovrfsr::kRcasDppTileH, "the host cuts its span records for 32-row bands");
-    static_assert(TH == 32 || TH == 16, "a wave's R rows must sit inside one 16-row mask group");
-    // (8 rows per lane: 10 loads per 8 pixels and half the per-thread prologue of the 4-row form: RCAS-only +2.7 % on batches)
-    const uint32_t img_i = blockIdx.z;
-    const int W = a.v.outW, H = a.v.outH;
-    OVRFSR_IMAGES(ovrfsr::FMT_RGBA8, OUT_FMT);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x, y, xEnd;
-    bool border;
-    if constexpr (SPANS) {
-        const uint32_t r0 = OVRFSR_SPAN_REC(a)[2 * blockIdx.x], r1 = OVRFSR_SPAN_REC(a)[2 * blockIdx.x + 1]; // uniform
-        const int x0 = (int)(r0 & 0xffffu), tileY = (int)(r0 >> 16);
-        xEnd = (int)r1;
-        x = x0 + lane - 1; y = tileY * TH + wave * R;
-        border = x0 == 0 || x0 + TW + 1 > W || tileY == 0 || (tileY + 1) * TH + 1 > H;
-    } else {
-        const uint32_t tilesX = (uint32_t)(W + TW - 1) / TW, tilesY = (uint32_t)(H + TH - 1) / TH;
-        const uint32_t tile = xcd_tile_index(blockIdx.x, tilesX * tilesY);
-        uint32_t tileX, tileY;
-        tile_xy(tile, tilesX, a.dppTilesXMagic, tileX, tileY);
-        x = (int)tileX * TW + lane - 1; y = (int)tileY * TH + wave * R;
-        xEnd = W;
-        // workgroup-uniform: does any tap of this block (columns -1..62, rows -1..16 of the tile) fall outside the image?
-        border = tileX == 0 || (int)(tileX + 1) * TW + 1 > W || tileY == 0 || (int)(tileY + 1) * TH + 1 > H;
-    }
-    if (y >= H) return; // wave-uniform
-    float4 c[R + 2];
-    if (border) {
-#pragma unroll
-        for (int i = 0; i < R + 2; ++i) c[i] = rcas_tap<ovrfsr::FMT_RGBA8, true>(in, a.v.in_pitch, x, y - 1 + i, W, H);
-    } else {
-#pragma unroll
-        for (int i = 0; i < R + 2; ++i) c[i] = rcas_tap<ovrfsr::FMT_RGBA8, false>(in, a.v.in_pitch, x, y - 1 + i, W, H);
-    }
-    const bool store = lane >= 1 && lane <= TW && x < xEnd;
-    [[maybe_unused]] bool inside = true;
-    if constexpr (SPANS) {
-        const uint32_t eye = (a.m.first_eye ^ (img_i & a.m.alternate)) & 1u;
-        const uint32_t mode = a.m.mode[eye];
-        inside = mode == ovrfsr::MASK_ALL_INSIDE ||
-                 (mode == ovrfsr::MASK_MIXED && x >= 0 && group_inside((uint32_t)x >> 4, (uint32_t)y >> 4, a.m.centre[eye], a.m.r2));
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const float4 e = c[i + 1];
-        const float4 d = make_float4(dpp_from_left(e.x), dpp_from_left(e.y), dpp_from_left(e.z), 0.0f);
-        const float4 f = make_float4(dpp_from_right(e.x), dpp_from_right(e.y), dpp_from_right(e.z), 0.0f);
-        float pr, pg, pb;
-        rcas_resolve_bytes<true>(c[i], d, e, f, c[i + 2], a.sharp, pr, pg, pb);
-        if constexpr (SPANS) {
-            if (!inside) { // byte domain: decode, tint, re-encode (identity without the debug tint)
-                const float mulG = 1.0f - 0.3f;
-                pr = e.x;
-                pg = a.debug ? (float)unit_to_unorm8(unorm8_to_unit(e.y) * mulG) : e.y;
-                pb = a.debug ? (float)unit_to_unorm8(unorm8_to_unit(e.z) * mulG) : e.z;
-            }
-        }
-        if (store && y + i < H) {
-            if constexpr (OUT_FMT == ovrfsr::FMT_RGBA8) {
-                *OVRFSR_AT(uint32_t, out + ((uint32_t)(y + i) * a.v.out_pitch + (uint32_t)x * 4u)) = pack_bytes_rne(pr, pg, pb);
-            } else {
-                const float s = 1.0f / 255.0f;
-                if (SPANS && !inside) { // the un-rounded tinted texel, as rcas_direct_kernel stores it
-                    const float mulG = 1.0f - (float)a.debug * 0.3f;
-                    store_unit<OUT_FMT>(out, a.v.out_pitch, x, y + i, unorm8_to_unit(e.x), unorm8_to_unit(e.y) * mulG, unorm8_to_unit(e.z) * mulG, 1.0f);
-                } else {
-                    store_unit<OUT_FMT>(out, a.v.out_pitch, x, y + i, pr * s, pg * s, pb * s, 1.0f);
-                }
-            }
-        }
-    }
+    constexpr bool EXACT = false;
+#include "fsr_rcas_dpp.inc"
+}
+// exact stores: the RGBA8 destination only, in the three forms launch_rcas takes (32 rows, 16 rows, span records)
+template <bool SPANS, int TH>
+__global__ __launch_bounds__(256) void rcas_dpp_exact_kernel(const ovrfsr::RcasArgs a)
+{
+    constexpr int OUT_FMT = ovrfsr::FMT_RGBA8;
+    constexpr bool EXACT = true;
+#include "fsr_rcas_dpp.inc"
 }
 #endif // !OVRFSR_STRICT
 

@@ -14,6 +14,9 @@ enum : int { FMT_R11G11B10F = 6 };
 // input-only: 4-sample RGBA8 (= OVRFSR_FORMAT_MS(OVRFSR_FORMAT_RGBA8_UNORM, 4)), resolved inside easu_fast_kernel's staging sweep
 enum : int { FMT_RGBA8_MS4 = 0x400 };
 enum : int { PREC_FP32 = 0, PREC_FP32_STRICT = 2 }; // ovrfsr_precision (1 is not a mode)
+// OVRFSR_PRECISION_FP32_EXACT: the product build everywhere; launch_rcas alone is handed this value and takes the guarded RCAS instances
+// (rcas_dpp_exact_kernel / rcas_direct_exact_kernel).  Every other launcher gets PREC_FP32 (PostProcessor::LaunchPrec)
+enum : int { PREC_FP32_EXACT = 3 };
 
 // mask_mode: every 16x16 group inside the radius / every group outside / mixed (test per group)
 enum : uint32_t { MASK_ALL_INSIDE = 0, MASK_ALL_OUTSIDE = 1, MASK_MIXED = 2 };

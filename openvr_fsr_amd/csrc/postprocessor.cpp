@@ -235,6 +235,19 @@ int PostProcessor::EnsureBuffer(DeviceBuffer &buf, size_t need)
     return OVRFSR_OK;
 }
 
+// OVRFSR_PRECISION_FP32_EXACT is the product build everywhere but in RCAS: every launcher and size rule except launch_rcas sees PREC_FP32
+int PostProcessor::LaunchPrec() const { return cfg_.precision == OVRFSR_PRECISION_FP32_EXACT ? (int)PREC_FP32 : cfg_.precision; }
+bool PostProcessor::ProductArithmetic() const { return LaunchPrec() == PREC_FP32; }
+
+// exact stores: the sharpen stage's destination must be RGBA8 too.  Known only once the call names its `out`; refused like a failed build
+int PostProcessor::CheckExactDestination(uint32_t format)
+{
+    if (cfg_.precision != OVRFSR_PRECISION_FP32_EXACT || !doSharpen_ || format == OVRFSR_FORMAT_RGBA8_UNORM || format == OVRFSR_FORMAT_BGRA8_UNORM)
+        return OVRFSR_OK; // (a BGRA8 destination is refused by ApplyPostProcess in every mode)
+    enabled_ = false;
+    return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must write RGBA8 (a half, float or 10-bit destination promises no exact bytes)");
+}
+
 uint32_t PostProcessor::IntermediateFormat() const
 {
     // quantize_intermediate=0 keeps fp32, whatever the format rule.
@@ -334,8 +347,18 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     if (cfg_.stage_mask < 0 || cfg_.stage_mask > 2) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "bad stage_mask");
     if (!doUpscale_ && (ow != in.width || oh != in.height))
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "sharpen-only needs output size == input size");
-    if (cfg_.precision != OVRFSR_PRECISION_FP32 && cfg_.precision != OVRFSR_PRECISION_FP32_STRICT)
+    if (cfg_.precision != OVRFSR_PRECISION_FP32 && cfg_.precision != OVRFSR_PRECISION_FP32_STRICT && cfg_.precision != OVRFSR_PRECISION_FP32_EXACT)
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "unknown precision");
+    if (cfg_.precision == OVRFSR_PRECISION_FP32_EXACT) {
+        // exact stores (header): promised where the sharpen stage is RCAS from RGBA8 to RGBA8 behind a quantised intermediate; every other
+        // configuration with a sharpen stage is refused -- nothing in it promises the strict build's bytes, so the mode must not pretend to
+        if (cfg_.use_nis) return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: NIS has no exact-stores form (use_nis)");
+        if (cfg_.fused == 1) return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form (fused = 1)");
+        if (doUpscale_ && doSharpen_ && !cfg_.quantize_intermediate)
+            return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read a UNORM8 intermediate (quantize_intermediate = 0)");
+        if (doSharpen_ && (doUpscale_ ? IntermediateFormat() : in.format) != OVRFSR_FORMAT_RGBA8_UNORM)
+            return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read RGBA8 (a half, float or 10-bit intermediate or input promises no exact bytes)");
+    }
 
     for (int eye = 0; eye < 2; ++eye) {
         mask_constants(centre_[eye], radius_, ow, oh, cfg_.proj_centre, cfg_.radius, textureContainsOnlyOneEye_ ? 1 : 0, eye);
@@ -347,7 +370,7 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
         if (rc != OVRFSR_OK) return rc;
     } else if (doUpscale_) {
         PrepareUpscalingResources();
-        const size_t lds = easu_lds_bytes(cfg_.precision, (int)in.format, cellsW_, cellsH_);
+        const size_t lds = easu_lds_bytes(LaunchPrec(), (int)in.format, cellsW_, cellsH_);
         if (lds > 64 * 1024) return Fail(OVRFSR_ERR_UNSUPPORTED, "scale ratio needs more LDS than one tile may use");
     }
     {
@@ -408,7 +431,7 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
         if (e == hipSuccess) e = hipMemcpy(bilinDev_, taps.data(), taps.size() * sizeof(BilinTap), hipMemcpyHostToDevice);
         if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("bilinear tap tables: ") + hipGetErrorString(e));
     }
-    if (doUpscale_ && cfg_.precision == OVRFSR_PRECISION_FP32 && (maskMode_[0] == MASK_MIXED || maskMode_[1] == MASK_MIXED)) {
+    if (doUpscale_ && ProductArithmetic() && (maskMode_[0] == MASK_MIXED || maskMode_[1] == MASK_MIXED)) {
         const bool nis = cfg_.use_nis != 0; // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
         int rc = PrepareTileLists(nis ? 32 : kTileW, nis ? 24 : kTileH, nis ? 32 : 16, nis ? 24 : 16);
         if (rc != OVRFSR_OK) return rc;
@@ -428,7 +451,7 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
         return Fail(OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for float images under reference_formats (UNORM8 intermediate of a float source)");
     const bool byteMidOfFloat = floatIn && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
     const bool autoFused = !tenBit && !byteMidOfFloat && cfg_.fused == -1 && tileListDev_ != nullptr && fusedCellsW_ <= 40 &&
-                           fused_lds_bytes(cfg_.precision, (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) <= kFusedLdsMax;
+                           fused_lds_bytes(LaunchPrec(), (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) <= kFusedLdsMax;
     // auto on a masked product-build EASU+RCAS pipeline: the two-pass kernels on the tiles touching the radius, tiles
     // outside written in final form (ApplySorted); cfg.fused = 1 keeps the single fused kernel on those tiles
     // Measured: with 4-byte pixels the sorted two-pass form wins (C2 shape, radius 0.5: +13 %); with 8/16-byte
@@ -438,11 +461,13 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     useSorted_ = cfg_.fused == -1 && tileListDev_ != nullptr && doUpscale_ && doSharpen_ && !cfg_.use_nis &&
                  (in.format == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
     if ((cfg_.fused == 1 || (autoFused && !useSorted_)) && doUpscale_ && doSharpen_ && !cfg_.use_nis) {
-        const bool pitchOk = cfg_.precision == OVRFSR_PRECISION_FP32_STRICT || fusedCellsW_ <= 40;
-        if (!pitchOk || fused_lds_bytes(cfg_.precision, (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) > kFusedLdsMax)
+        const bool pitchOk = LaunchPrec() == PREC_FP32_STRICT || fusedCellsW_ <= 40;
+        if (!pitchOk || fused_lds_bytes(LaunchPrec(), (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) > kFusedLdsMax)
             return Fail(OVRFSR_ERR_UNSUPPORTED, "fused kernel: tile footprint does not fit LDS at this scale");
         useFused_ = true;
     }
+    if (useFused_ && cfg_.precision == OVRFSR_PRECISION_FP32_EXACT) // (fused = -1 picks it for half / float intermediates only, refused above)
+        return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form");
     if (cfg_.debug_mode) {
         // every slot is checked on its own: a creation that failed half-way through the ring (found by fault injection, round 6: slot 0 existed,
         // a later one did not, and the rebuild after reset skipped the whole ring -- hipEventRecord on a null event) is completed by the next build
@@ -700,14 +725,14 @@ int PostProcessor::ApplyUpscaling(uint32_t n, int firstEye, int alternate, const
         na.tilesX = (out.width + 31) / 32;   // Dispatch(ceil(outW/32), ceil(outH/24)), :397
         na.tilesY = (out.height + 23) / 24;
         na.tileList = nullptr;
-        if (!tileListDev_) return Launched(launch_nis_scaler(cfg_.precision, (int)in.format, (int)out.format, na, n, stream), "NVScaler");
+        if (!tileListDev_) return Launched(launch_nis_scaler(LaunchPrec(), (int)in.format, (int)out.format, na, n, stream), "NVScaler");
         return ForEachEyePass(n, firstEye, alternate, in, stream, "NVScaler", [&](const EyePass &ps, hipStream_t aux) {
             NisArgs b = na;
             ps.Select(b);
             hipError_t e = hipSuccess;
             if (nInside_[ps.eye]) {
                 b.tileList = tileListDev_ + listOffInside_[ps.eye];
-                e = launch_nis_scaler(cfg_.precision, (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
+                e = launch_nis_scaler(LaunchPrec(), (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
             }
             if (e == hipSuccess && nOutside_[ps.eye]) {
                 b.tileList = tileListDev_ + listOffOutside_[ps.eye];
@@ -719,14 +744,14 @@ int PostProcessor::ApplyUpscaling(uint32_t n, int firstEye, int alternate, const
     }
     EasuArgs a;
     FillEasu(a, in, inStride, out, outStride, firstEye, alternate);
-    if (!tileListDev_) return Launched(launch_easu(cfg_.precision, (int)in.format, (int)out.format, a, n, stream), "EASU");
+    if (!tileListDev_) return Launched(launch_easu(LaunchPrec(), (int)in.format, (int)out.format, a, n, stream), "EASU");
     return ForEachEyePass(n, firstEye, alternate, in, stream, "EASU", [&](const EyePass &ps, hipStream_t aux) {
         EasuArgs b = a;
         ps.Select(b);
         hipError_t e = hipSuccess;
         if (nInside_[ps.eye]) {
             b.tileList = tileListDev_ + listOffInside_[ps.eye];
-            e = launch_easu(cfg_.precision, (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
+            e = launch_easu(LaunchPrec(), (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
         }
         if (e == hipSuccess && nOutside_[ps.eye]) {
             b.tileList = tileListDev_ + listOffOutside_[ps.eye];
@@ -834,7 +859,7 @@ int PostProcessor::ApplySorted(uint32_t n, int firstEye, int alternate, const ov
         if (nInside_[eye]) {
             em.tileList = tileListDev_ + listOffInside_[eye];
             em.ringStrips = 1; // of a ring tile, RCAS only reads the pixels next to an inside tile
-            e = launch_easu(cfg_.precision, (int)in.format, (int)mid.format, em, ps.cnt, stream, nInside_[eye] + nRing_[eye]);
+            e = launch_easu(LaunchPrec(), (int)in.format, (int)mid.format, em, ps.cnt, stream, nInside_[eye] + nRing_[eye]);
         }
         if (e == hipSuccess && nOutside_[eye]) {
             eo.tileList = tileListDev_ + listOffOutside_[eye];
@@ -858,7 +883,7 @@ int PostProcessor::ApplyFused(uint32_t n, int firstEye, int alternate, const ovr
     std::memcpy(&a.sharp, &rcasCon_[0], 4);
     a.cellsW = fusedCellsW_; a.cellsH = fusedCellsH_;
     const int midFormat = (int)IntermediateFormat();
-    if (!tileListDev_) return Launched(launch_fused(cfg_.precision, (int)in.format, midFormat, (int)out.format, a, n, stream), "fused EASU+RCAS");
+    if (!tileListDev_) return Launched(launch_fused(LaunchPrec(), (int)in.format, midFormat, (int)out.format, a, n, stream), "fused EASU+RCAS");
     // masked: tiles entirely outside the radius never need an intermediate (RCAS there is a tinted copy), they are
     // written in final form by the LDS-free bilinear kernel; only tiles touching the radius run the fused kernel
     EasuArgs ea;
@@ -870,7 +895,7 @@ int PostProcessor::ApplyFused(uint32_t n, int firstEye, int alternate, const ovr
         hipError_t e = hipSuccess;
         if (nInside_[ps.eye]) {
             fb.tileList = tileListDev_ + listOffInside_[ps.eye];
-            e = launch_fused(cfg_.precision, (int)in.format, midFormat, (int)out.format, fb, ps.cnt, stream, nInside_[ps.eye]);
+            e = launch_fused(LaunchPrec(), (int)in.format, midFormat, (int)out.format, fb, ps.cnt, stream, nInside_[ps.eye]);
         }
         if (e == hipSuccess && nOutside_[ps.eye]) {
             eb.tileList = tileListDev_ + listOffOutside_[ps.eye];
@@ -891,7 +916,7 @@ int PostProcessor::ApplySharpening(uint32_t n, int firstEye, int alternate, cons
         na.tilesX = (out.width + 31) / 32;   // Dispatch(ceil(outW/32), ceil(outH/32)), :492
         na.tilesY = (out.height + 31) / 32;
         na.tileList = nullptr;
-        return Launched(launch_nis_sharpen(cfg_.precision, (int)in.format, (int)out.format, na, n, stream), "NVSharpen");
+        return Launched(launch_nis_sharpen(LaunchPrec(), (int)in.format, (int)out.format, na, n, stream), "NVSharpen");
     }
     RcasArgs a;
     FillRcas(a, in, inStride, out, outStride, firstEye, alternate);
@@ -912,7 +937,7 @@ bool PostProcessor::ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image 
     const bool unmasked = !tileListDev_ && maskMode_[0] == MASK_ALL_INSIDE && maskMode_[1] == MASK_ALL_INSIDE;
     const uint32_t easuOut = doSharpen_ ? IntermediateFormat() : out.format;
     return in.format == (uint32_t)FMT_RGBA8_MS4 && doUpscale_ && !cfg_.use_nis && !useSorted_ && !useFused_ && unmasked &&
-           easu_msaa_fused_ok(cfg_.precision, (int)easuOut, cellsW_);
+           easu_msaa_fused_ok(LaunchPrec(), (int)easuOut, cellsW_);
 #endif
 }
 
@@ -1075,6 +1100,8 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
     // RESOLVED destination -- the caller's buffer or the ctx-owned one: chaining the previous ctx-owned result back in as `in`
     // (sharpen-only mode, where the sizes agree) is the same race
     if (stages && RangesOverlap(*in, 0, dst, 0, 1)) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "input and output images overlap");
+    rc = CheckExactDestination(dst.format);
+    if (rc != OVRFSR_OK) return rc;
 
     lastApplyRecorded_ = false;
     if (pairMode) {
@@ -1181,6 +1208,8 @@ int PostProcessor::ApplyBatch(uint32_t n, int firstEye, int alternate, const ovr
     }
     if (out0->width != outputWidth_ || out0->height != outputHeight_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
     if (!(doUpscale_ || doSharpen_)) return Fail(OVRFSR_ERR_UNSUPPORTED, "no stage selected (render_scale == 1 with NIS off would still sharpen)");
+    rc = CheckExactDestination(out0->format);
+    if (rc != OVRFSR_OK) return rc;
     return ApplyPostProcess(n, firstEye, alternate, *in0, inStride, *out0, outStride, stream);
 }
 

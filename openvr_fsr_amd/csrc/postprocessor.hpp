@@ -158,6 +158,9 @@ private:
     int EnsureBuffer(DeviceBuffer &buf, size_t need);
     int IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride); // the upscale stage's destination in front of a sharpening stage
     static bool RangesOverlap(const ovrfsr_image &in0, size_t inStride, const ovrfsr_image &out0, size_t outStride, uint32_t n);
+    int LaunchPrec() const;
+    bool ProductArithmetic() const;
+    int CheckExactDestination(uint32_t format);
     uint32_t IntermediateFormat() const;
     uint32_t OwnedFormat(uint32_t submitted) const;
     bool ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const;

@@ -23,7 +23,16 @@ it): UNORM8 stores of FLOAT sources -- the UNORM8 intermediate of an RGBA16F / R
 content and every HDR kind of tests/test_gpu_formats.py::_hdr_image (the structured image scaled x2 / x6 / x40; a dark image with 2 % highlights
 at x6 / x40 / x400), masked (mask-sorted form, radius 0.5) and unmasked, at the three LDS pitches of easu_fast_kernel (28: x4/3, 32: x1.3,
 40: x1.11).  The guard's band there is 2^-9 byte x max(1, largest texel of the tile's footprint): the distance is reported as a fraction of
-the band of the pixel it was met at."""
+the band of the pixel it was met at.
+
+    OVRFSR_LIB=$PWD/ab/audit.so python tools/debug/tie_audit.py --rcas [scale=1.0] [seed_offset=0]
+
+runs ONLY the campaign of OVRFSR_PRECISION_FP32_EXACT (exact stores): the guarded RCAS instances re-evaluate every stored pixel in the
+reference's operator order and count the unlisted ones whose product byte differs.  Structured, uniform-random and natural content and the
+tie-rich fixture (tests/rcas_ties.py); sharpness 0, 0.5, 0.9 and 1; the unmasked pipeline, the mask-sorted one (radius 0.5: span records) and
+RCAS alone; each as one image per call and as a batch, so that rcas_dpp_kernel runs in its 16-row and its 32-row form.  BASELINE's C2 shape at
+scale >= 1, a quarter of it per axis below.  The largest |product - reference-order| distance this prints at scale 1 is what the band
+(kRcasTieBits, fsr_kernels.inc) is derived from: the smallest power of two that is at least 3 times it (profiles/exact_stores.txt)."""
 import ctypes
 import os
 import sys
@@ -171,9 +180,85 @@ def main_reference_formats(argv):
     sys.exit(1 if total["flips"] else 0)
 
 
+def counters_rcas(reset=False):
+    fn = A.library().ovrfsr_debug_tie_audit_rcas      # AttributeError: not an audit build
+    fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
+    buf = (ctypes.c_ulonglong * 5)()
+    assert fn(buf, 1 if reset else 0) == 0
+    v = list(buf)
+    return {"audited": v[0], "listed": v[1], "flips": v[2], "dist": float(np.uint32(v[3] & 0xffffffff).view(np.float32)), "band_bits": v[4]}
+
+
+def dpp_rows(ow, oh, n):
+    """rows per workgroup rcas_dpp_kernel takes for an unmasked launch of n images (fsr_kernels.hip, rcas_dpp_small)"""
+    wgs = ((ow + 61) // 62) * ((oh + 31) // 32) * n
+    full, half = (wgs + 2047) // 2048, (2 * wgs + 2047) // 2048
+    return 16 if wgs < 16 * 2048 and 103 * half < 200 * full else 32
+
+
+def run_rcas(tag, texs, outW, outH, content, sharp, **cfg):
+    n = texs.shape[0]
+    outs = torch.empty((n, outH, outW, 4), dtype=torch.uint8, device=DEV)
+    pp = A.PostProcessor(fsr_enabled=1, out_width=outW, out_height=outH, sharpness=sharp, precision=A.PRECISION_FP32_EXACT, **cfg)
+    counters_rcas(reset=True)
+    pp.apply_batch(texs, outs, first_eye=A.EYE_LEFT, alternate_eyes=True)
+    torch.cuda.synchronize()
+    c = counters_rcas()
+    pp.close()
+    print("%-34s %-10s sharp %-4g n=%3d  audited %11d  listed %9d (%6.3f %%)  FLIPS %d  max dist %.3e byte"
+          % (tag, content, sharp, n, c["audited"], c["listed"], 100.0 * c["listed"] / max(1, c["audited"]), c["flips"], c["dist"]), flush=True)
+    return c
+
+
+def main_rcas(argv):
+    from tests import rcas_ties
+    k = float(argv[0]) if argv else 1.0
+    seed = 0x5EED0000 + (int(argv[1], 0) if len(argv) > 1 else 0)
+    iw, ih, ow, oh = (1683, 1869, 2244, 2492) if k >= 1.0 else (420, 467, 560, 623)
+    want = max(2, int(round(8 * k)) & ~1)
+    n32 = next(n for n in range(want, want + 64, 2) if dpp_rows(ow, oh, n) == 32)   # a batch that takes the 32-row form
+    assert dpp_rows(ow, oh, 1) == 16
+    total = {"audited": 0, "listed": 0, "flips": 0, "dist": 0.0}
+    per = {}
+    t0 = time.time()
+
+    def acc(content, c):
+        p = per.setdefault(content, [0, 0])
+        p[0] += c["audited"]; p[1] += c["listed"]
+        for key in ("audited", "listed", "flips"):
+            total[key] += c[key]
+        total["dist"] = max(total["dist"], c["dist"])
+        total["band_bits"] = c["band_bits"]
+
+    for content in ("structured", "random", "natural"):
+        for sharp in (0.0, 0.5, 0.9, 1.0):
+            for n, rows in ((1, 16), (n32, 32)):
+                seed += 1000
+                acc(content, run_rcas("pipeline unmasked, %d-row" % rows, CONTENT[content](n, iw, ih, seed), ow, oh, content, sharp, radius=2.0))
+                acc(content, run_rcas("RCAS only, %d-row" % rows, CONTENT[content](n, ow, oh, seed + 1), ow, oh, content, sharp, radius=2.0, stage_mask=2))
+            seed += 1000
+            acc(content, run_rcas("pipeline radius 0.5 (spans)", CONTENT[content](n32, iw, ih, seed), ow, oh, content, sharp, radius=0.5))
+            acc(content, run_rcas("RCAS only radius 0.5", CONTENT[content](2, ow, oh, seed + 1), ow, oh, content, sharp, radius=0.5, stage_mask=2))
+    fix = torch.from_numpy(np.ascontiguousarray(rcas_ties.fixture(7)[0])).to(DEV)
+    S = rcas_ties.SIZE
+    assert dpp_rows(S, S, 1) == 16 and dpp_rows(S, S, 192) == 32
+    for sharp in (0.0, 0.5, 0.9, 1.0):
+        for n in (1, 192):
+            acc("tie-rich", run_rcas("RCAS only, %d-row" % dpp_rows(S, S, n), fix[None].expand(n, -1, -1, -1).contiguous(), S, S, "tie-rich", sharp, radius=2.0, stage_mask=2))
+    band = 2.0 ** -total["band_bits"]
+    for content, (a, l) in per.items():
+        print("LISTED %-10s %.4f %% of %d pixels (band 2^-%d byte)" % (content, 100.0 * l / max(1, a), a, total["band_bits"]))
+    print("TOTAL audited %d pixels, listed %d (%.3f %%), FLIPS %d, max |product - reference-order| %.3e byte = %.3f of the band (2^-%d byte)   [%.0f s]"
+          % (total["audited"], total["listed"], 100.0 * total["listed"] / max(1, total["audited"]), total["flips"], total["dist"], total["dist"] / band,
+             total["band_bits"], time.time() - t0))
+    sys.exit(1 if total["flips"] else 0)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--reference-formats":
         return main_reference_formats(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--rcas":
+        return main_rcas(sys.argv[2:])
     k = float(sys.argv[1]) if len(sys.argv) > 1 else 1.0
     N = lambda n: max(2, int(round(n * k)) & ~1)  # noqa: E731
     total = {"audited": 0, "listed": 0, "flips": 0, "small_half_diffs": 0, "max_dist_bytes": 0.0, "max_dist_half_spacings": 0.0}
