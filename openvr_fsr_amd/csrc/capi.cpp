@@ -50,7 +50,6 @@ int guarded(F &&f) noexcept
         return OVRFSR_ERR_INVALID_ARGUMENT;
     }
 }
-constexpr uint32_t kMaxExtent = 16384; // same limit CheckImage puts on caller images
 } // namespace
 
 extern "C" {
@@ -112,22 +111,7 @@ OVRFSR_API void ovrfsr_config_default(ovrfsr_config *cfg)
 OVRFSR_API int ovrfsr_output_size(const ovrfsr_config *cfg, uint32_t in_w, uint32_t in_h, uint32_t *out_w, uint32_t *out_h)
 {
     if (!config_ok(cfg) || !out_w || !out_h) return OVRFSR_ERR_INVALID_ARGUMENT;
-    if (cfg->out_width != 0 && cfg->out_height != 0) {
-        if (cfg->out_width > kMaxExtent || cfg->out_height > kMaxExtent) return OVRFSR_ERR_INVALID_ARGUMENT;
-        *out_w = cfg->out_width;
-        *out_h = cfg->out_height;
-        return OVRFSR_OK;
-    }
-    // uint32 <- float truncation, PostProcessor.cpp:512-518.  A zero, negative or non-finite scale (a typo in
-    // openvr_mod.cfg) has no defined uint conversion, and a tiny one asks for an unbounded image: both are rejected,
-    // like any size beyond the 16384 texels an image may have here.
-    const float s = cfg->render_scale;
-    if (!std::isfinite(s) || !(s > 0.f)) return OVRFSR_ERR_INVALID_ARGUMENT;
-    const float fw = s < 1.f ? in_w / s : in_w * s, fh = s < 1.f ? in_h / s : in_h * s;
-    if (!(fw < (float)(kMaxExtent + 1)) || !(fh < (float)(kMaxExtent + 1))) return OVRFSR_ERR_INVALID_ARGUMENT;
-    *out_w = (uint32_t)fw;
-    *out_h = (uint32_t)fh;
-    return OVRFSR_OK;
+    return ovrfsr::plan_output_size(*cfg, in_w, in_h, out_w, out_h);
 }
 
 OVRFSR_API int ovrfsr_create(int device, const ovrfsr_config *cfg, ovrfsr_ctx **out_ctx)

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include "postprocessor.hpp"
+#include "pipeline_plan.h"
 
 namespace ovrfsr {
 

@@ -203,21 +203,6 @@ __global__ __launch_bounds__(256) void packed_resolve_kernel(const uint8_t *__re
 
 namespace ovrfsr {
 
-// LDS row pitch (cells) of the product-build EASU kernel; 0 = footprint too wide, use the generic kernel
-int easu_fast_pitch(int cellsW) { return cellsW <= 32 ? 32 : cellsW <= 40 ? 40 : 0; }
-// the EASU-only kernel also has a 28-cell pitch: exactly the footprint of a 32-pixel tile at scale 3/4
-static int easu_kernel_pitch(int cellsW) { return cellsW <= 28 ? 28 : easu_fast_pitch(cellsW); }
-
-size_t easu_lds_bytes(int prec, int in_fmt, int cellsW, int cellsH)
-{
-    if (prec != PREC_FP32_STRICT && easu_fast_pitch(cellsW) != 0)
-        return (size_t)easu_fast_pitch(cellsW) * cellsH * (16 + 16 + 4) + (size_t)easu_fast_pitch(cellsW) * kLumPadRows * 4; // pitch 32/40 (the fused kernel's; 28 fits inside) + kLumPadRows
-    const bool wide = (prec == PREC_FP32_STRICT) || (in_fmt == FMT_RGBA32F) || (in_fmt == FMT_RGB10A2);
-    const size_t ncell = (size_t)cellsW * cellsH;
-    const size_t col = (ncell * (wide ? 16 : 8) + 15) & ~(size_t)15;
-    return col + ncell * 16 + ncell * 4;
-}
-
 template <int I, int O, bool M>
 static void easu_fast_go(int pitch, const EasuArgs &a, dim3 grid, hipStream_t s)
 {
@@ -305,21 +290,6 @@ static hipError_t rcas_go(bool strict, bool exact, const RcasArgs &a, dim3 grid,
     return hipGetLastError();
 }
 
-// LDS of the fused kernel: EASU planes + 34x34 intermediate (float4 cells)
-size_t fused_lds_bytes(int prec, int in_fmt, int mid_fmt, int cellsW, int cellsH)
-{
-    size_t e = easu_lds_bytes(prec, in_fmt, cellsW, cellsH);
-    e = (e + 15) & ~(size_t)15;
-    size_t midCell = 16;
-    if (prec != PREC_FP32_STRICT && easu_fast_pitch(cellsW) != 0) {
-        const size_t ncell = (size_t)easu_fast_pitch(cellsW) * cellsH;
-        // the luma plane doubles as the near-tie list region (fused_kernel) and is at least that large
-        if (ncell * 4 < kFusedTieListBytes) e += kFusedTieListBytes;
-    }
-    (void)mid_fmt;
-    return e + (size_t)(kTileW + 2) * (kTileH + 2) * midCell;
-}
-
 template <int I, int M, int O>
 static hipError_t fused_go3(bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
 {
@@ -403,13 +373,9 @@ static hipError_t easu_outside_go(int mid_fmt, const EasuArgs &a, dim3 grid, hip
 // nTiles blocks, each resolving tile a.tileList[block]: tiles entirely outside the radius (product build only).
 // mid_fmt < 0: EASU pass only; mid_fmt >= 0: write the FINAL pixel of the EASU->RCAS pipeline (RCAS outside the radius
 // is a tinted copy of the intermediate texel, so the intermediate's format rounding is applied in registers).
-// LDS-staged outside-tile kernel (outside_staged_kernel): upscaling only, RGBA8 sources (any destination format).
-// RGBA16F sources stay on the per-pixel kernel: stand-alone the staged form is 11 % faster there too (C5: 1020 -> 904 us),
-// but its 20 KB of LDS per workgroup cannot co-reside with three 52 KB fused-kernel workgroups per CU, and the overlapped
-// step gets 20 % slower.
+// LDS-staged outside-tile kernel (outside_staged_kernel): where outside_staged_ok (fsr_sizes.h) says so.
 // mid_fmt < 0: the EASU pass alone; >= 0: final pixel = tint(value read back from a mid_fmt intermediate), RGBA32F = tint
 // of the un-rounded value (also NIS DirectCopy, tileH = 24).
-bool outside_staged_ok(const BatchView &v, int in_fmt) { return v.inW <= v.outW && v.inH <= v.outH && in_fmt == FMT_RGBA8; }
 
 template <int TH, int I, int O>
 static hipError_t outside_staged_go(int mid_fmt, const OutsideArgs &a, dim3 grid, hipStream_t s)
@@ -490,12 +456,6 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
     launch_fresh();
     hipLaunchKernelGGL(bgra_to_rgba_kernel, dim3((w + 255) / 256, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h);
     return hipGetLastError();
-}
-
-// rows of the resolve pass's destination: texels of the format the pipeline sees (R11G11B10F: 4-byte words in, RGBA16F out), padded to 16 bytes
-uint32_t resolve_pitch(int fmt, uint32_t w)
-{
-    return (w * texel_bytes(pipeline_format((uint32_t)fmt)) + 15u) & ~15u;
 }
 
 // one launch of the resolve pass: what both resolve kernels take, and where they run
@@ -643,11 +603,6 @@ hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, 
         return hipGetLastError();
     }
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_go, strict, a, grid, lds, s)
-}
-
-bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW)
-{
-    return prec == PREC_FP32 && out_fmt == FMT_RGBA8 && easu_kernel_pitch(cellsW) != 0;
 }
 
 hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)

@@ -3,9 +3,9 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include "fsr_params.h"
+#include "fsr_sizes.h" // the size rules the launchers go by (and the pipeline planner decides by)
 
 namespace ovrfsr {
-size_t easu_lds_bytes(int prec, int in_fmt, int cellsW, int cellsH);
 // HIP keeps a host thread's last error until somebody reads it, and a kernel launch reports its failure only there.  Every launch_* below
 // reads (= clears) it BEFORE launching, so that what it returns afterwards is its own launch's -- not an error the HOST's code left behind:
 // a failed hipMalloc of the caller's, handled through its return value, used to fail the next frame as "EASU launch: out of memory"
@@ -14,11 +14,8 @@ inline void launch_fresh() { (void)hipGetLastError(); }
 
 hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a, uint32_t batch, hipStream_t s, uint32_t nTiles = 0);
 hipError_t launch_easu_outside(int in_fmt, int mid_fmt, int out_fmt, const EasuArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
-size_t fused_lds_bytes(int prec, int in_fmt, int mid_fmt, int cellsW, int cellsH);
 hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const FusedArgs &a, uint32_t batch, hipStream_t s, uint32_t nTiles = 0);
 hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a, uint32_t batch, hipStream_t s, uint32_t nTiles = 0);
-int nis_pitch(int cellsW);
-size_t nis_scaler_lds_bytes(int cellsW, int cellsH);
 hipError_t launch_nis_scaler(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s, uint32_t nGroups = 0);
 hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
                               uint32_t batch, hipStream_t s);
@@ -26,13 +23,9 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
 // dst + i * h * resolve_pitch(fmt, w), rows resolve_pitch(fmt, w) bytes apart (the row bytes rounded up to 16)
 // fmt FMT_R11G11B10F (samples 1, 2, 4 or 8): 4-byte packed texels in, RGBA16F texels out -- the one source whose destination texel
 // has another size: resolve_pitch(FMT_R11G11B10F, w) is the pitch of the 8-byte copy
-uint32_t resolve_pitch(int fmt, uint32_t w);
-// 4-sample RGBA8 input resolved inside easu_fast_kernel's staging sweep (in_fmt FMT_RGBA8_MS4 of launch_easu): product build, unmasked,
-// UNORM8 destination (the pipeline's intermediate or an EASU-only output), a fixed LDS pitch
-bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW);
+// (resolve_pitch, easu_msaa_fused_ok -- FMT_RGBA8_MS4 resolved inside easu_fast_kernel's staging sweep -- and outside_staged_ok: fsr_sizes.h)
 hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
                           uint32_t batch, hipStream_t s);
-bool outside_staged_ok(const BatchView &v, int in_fmt);
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a, uint32_t nGroups, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s);

@@ -15,7 +15,7 @@ enum : int { FMT_R11G11B10F = 6 };
 enum : int { FMT_RGBA8_MS4 = 0x400 };
 enum : int { PREC_FP32 = 0, PREC_FP32_STRICT = 2 }; // ovrfsr_precision (1 is not a mode)
 // OVRFSR_PRECISION_FP32_EXACT: the product build everywhere; launch_rcas alone is handed this value and takes the guarded RCAS instances
-// (rcas_dpp_exact_kernel / rcas_direct_exact_kernel).  Every other launcher gets PREC_FP32 (PostProcessor::LaunchPrec)
+// (rcas_dpp_exact_kernel / rcas_direct_exact_kernel).  Every other launcher gets PREC_FP32 (Plan::launchPrec)
 enum : int { PREC_FP32_EXACT = 3 };
 
 // mask_mode: every 16x16 group inside the radius / every group outside / mixed (test per group)

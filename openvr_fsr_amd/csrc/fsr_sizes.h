@@ -1,0 +1,65 @@
+// fsr_sizes.h -- the size rules of the kernels: LDS pitches, LDS bytes, and which kernel a shape may take.  Host only, inline, no HIP call:
+// the pipeline planner (pipeline_plan.cpp) decides by them and the launchers (fsr_kernels.hip, nis_kernels.hip) launch by them, so that
+// what the planner accepts is what the launchers can run.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "fsr_formats.h"
+#include "fsr_params.h"
+
+namespace ovrfsr {
+
+// LDS row pitch (cells) of the product-build EASU kernel; 0 = footprint too wide, use the generic kernel
+inline int easu_fast_pitch(int cellsW) { return cellsW <= 32 ? 32 : cellsW <= 40 ? 40 : 0; }
+// the EASU-only kernel also has a 28-cell pitch: exactly the footprint of a 32-pixel tile at scale 3/4
+inline int easu_kernel_pitch(int cellsW) { return cellsW <= 28 ? 28 : easu_fast_pitch(cellsW); }
+
+inline size_t easu_lds_bytes(int prec, int in_fmt, int cellsW, int cellsH)
+{
+    if (prec != PREC_FP32_STRICT && easu_fast_pitch(cellsW) != 0)
+        return (size_t)easu_fast_pitch(cellsW) * cellsH * (16 + 16 + 4) + (size_t)easu_fast_pitch(cellsW) * kLumPadRows * 4; // pitch 32/40 (the fused kernel's; 28 fits inside) + kLumPadRows
+    const bool wide = (prec == PREC_FP32_STRICT) || (in_fmt == FMT_RGBA32F) || (in_fmt == FMT_RGB10A2);
+    const size_t ncell = (size_t)cellsW * cellsH;
+    const size_t col = (ncell * (wide ? 16 : 8) + 15) & ~(size_t)15;
+    return col + ncell * 16 + ncell * 4;
+}
+
+// LDS of the fused kernel: EASU planes + 34x34 intermediate (float4 cells)
+inline size_t fused_lds_bytes(int prec, int in_fmt, int mid_fmt, int cellsW, int cellsH)
+{
+    size_t e = easu_lds_bytes(prec, in_fmt, cellsW, cellsH);
+    e = (e + 15) & ~(size_t)15;
+    size_t midCell = 16;
+    if (prec != PREC_FP32_STRICT && easu_fast_pitch(cellsW) != 0) {
+        const size_t ncell = (size_t)easu_fast_pitch(cellsW) * cellsH;
+        // the luma plane doubles as the near-tie list region (fused_kernel) and is at least that large
+        if (ncell * 4 < kFusedTieListBytes) e += kFusedTieListBytes;
+    }
+    (void)mid_fmt;
+    return e + (size_t)(kTileW + 2) * (kTileH + 2) * midCell;
+}
+
+// NVScaler: LDS row pitch (cells) of a 32x24 group's footprint; 0 = too wide
+inline int nis_pitch(int cellsW) { return cellsW <= 32 ? 32 : cellsW <= 40 ? 40 : 0; }
+inline size_t nis_scaler_lds_bytes(int cellsW, int cellsH) { return (size_t)nis_pitch(cellsW) * cellsH * (4 + 4 + 16 + 4) + 2 * 512 * 4; } // Yu, Y255, E, raw texel
+
+// LDS-staged outside-tile kernel (outside_staged_kernel): upscaling only, RGBA8 sources (any destination format).
+// RGBA16F sources stay on the per-pixel kernel: stand-alone the staged form is 11 % faster there too (C5: 1020 -> 904 us),
+// but its 20 KB of LDS per workgroup cannot co-reside with three 52 KB fused-kernel workgroups per CU, and the overlapped
+// step gets 20 % slower.
+inline bool outside_staged_ok(const BatchView &v, int in_fmt) { return v.inW <= v.outW && v.inH <= v.outH && in_fmt == FMT_RGBA8; }
+
+// 4-sample RGBA8 input resolved inside easu_fast_kernel's staging sweep (in_fmt FMT_RGBA8_MS4 of launch_easu): product build, unmasked,
+// UNORM8 destination (the pipeline's intermediate or an EASU-only output), a fixed LDS pitch
+inline bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW)
+{
+    return prec == PREC_FP32 && out_fmt == FMT_RGBA8 && easu_kernel_pitch(cellsW) != 0;
+}
+
+// rows of the resolve pass's destination: texels of the format the pipeline sees (R11G11B10F: 4-byte words in, RGBA16F out), padded to 16 bytes
+inline uint32_t resolve_pitch(int fmt, uint32_t w)
+{
+    return (w * texel_bytes(pipeline_format((uint32_t)fmt)) + 15u) & ~15u;
+}
+
+} // namespace ovrfsr

@@ -1,0 +1,475 @@
+// pipeline_plan.cpp -- see pipeline_plan.h.  Host arithmetic only: this unit includes no HIP header and links against constants.cpp and
+// nis_config.cpp alone.  Reference: src/postprocess/PostProcessor.cpp (PrepareResources and what it calls).
+#include "pipeline_plan.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <utility>
+#include "fsr_formats.h"
+#include "fsr_sizes.h"
+
+namespace ovrfsr {
+
+namespace {
+
+enum RefusalId {
+    R_OUTPUT_SIZE, R_STAGE_MASK, R_SHARPEN_ONLY_SIZE, R_PRECISION, R_EXACT_NIS, R_EXACT_FUSED_ASKED, R_EXACT_FLOAT_MID, R_EXACT_SOURCE,
+    R_NIS_SCALE, R_NIS_LDS, R_EASU_LDS, R_FUSED_TEN_BIT, R_FUSED_FLOAT_REFERENCE, R_FUSED_LDS, R_EXACT_FUSED,
+    R_DEST_INPUT_ONLY, R_DEST_TEN_BIT_PAIR, R_DEST_TEN_BIT_MID, R_DEST_EXACT, R_COUNT
+};
+// in the order they are tested.  Status and text are part of the library's behaviour (tests/golden/launch_forms_parent.json).
+const Refusal kRefusals[R_COUNT] = {
+    {OVRFSR_ERR_INVALID_ARGUMENT, "output size is zero or beyond 16384 texels (render_scale must be finite and > 0)", true},
+    {OVRFSR_ERR_INVALID_ARGUMENT, "bad stage_mask", true},
+    {OVRFSR_ERR_INVALID_ARGUMENT, "sharpen-only needs output size == input size", true},
+    {OVRFSR_ERR_INVALID_ARGUMENT, "unknown precision", true},
+    // exact stores (header): promised where the sharpen stage is RCAS from RGBA8 to RGBA8 behind a quantised intermediate; every other
+    // configuration with a sharpen stage is refused -- nothing in it promises the strict build's bytes, so the mode must not pretend to
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: NIS has no exact-stores form (use_nis)", true},
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form (fused = 1)", true},
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read a UNORM8 intermediate (quantize_intermediate = 0)", true},
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read RGBA8 (a half, float or 10-bit intermediate or input promises no exact bytes)", true},
+    // (the reference ignores a `false` result of NVScalerUpdateConfig and dispatches with a half-filled block; that is undefined there, so it is an error here)
+    {OVRFSR_ERR_UNSUPPORTED, "NIS scales 1x..2x only (NVScalerUpdateConfig returned false)", true},
+    {OVRFSR_ERR_UNSUPPORTED, "NIS tile does not fit LDS", true},
+    {OVRFSR_ERR_UNSUPPORTED, "scale ratio needs more LDS than one tile may use", true},
+    {OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for RGB10A2 images", true},
+    {OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for float images under reference_formats (UNORM8 intermediate of a float source)", true},
+    {OVRFSR_ERR_UNSUPPORTED, "fused kernel: tile footprint does not fit LDS at this scale", true},
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form", true},
+    // the destination's: known only once the call names its `out`.  (Of the input-only formats only single-sample BGRA8 gets this far:
+    // CheckImage refuses R11G11B10F and multisampled destinations.)
+    {OVRFSR_ERR_UNSUPPORTED, input_only(OVRFSR_FORMAT_BGRA8_UNORM), false},
+    {OVRFSR_ERR_UNSUPPORTED, "RGB10A2 images pair with an RGB10A2 (or RGBA32F) destination only", false},
+    {OVRFSR_ERR_UNSUPPORTED, "RGB10A2 pipelines keep a 10-bit intermediate (quantize_intermediate = 1)", false},
+    {OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must write RGBA8 (a half, float or 10-bit destination promises no exact bytes)", true},
+};
+
+// a*b+c with two roundings, identical to the kernels' mad_unfused (separate statements)
+inline float mad2(float a, float b, float c)
+{
+    volatile float t = a * b;
+    return t + c;
+}
+
+inline float con_float(uint32_t bits)
+{
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+
+// LDS footprints of the EASU kernels' tiles (cells per axis, max over tiles)
+void easu_footprints(Plan &p)
+{
+    easu_con(p.easuCon, (float)p.inputWidth, (float)p.inputHeight, (float)p.inputWidth, (float)p.inputHeight, (float)p.outputWidth, (float)p.outputHeight);
+    const float sx = con_float(p.easuCon[0]), sy = con_float(p.easuCon[1]), cx = con_float(p.easuCon[2]), cy = con_float(p.easuCon[3]);
+    // LDS footprint of one 32x32 output tile: f-texel of first and last pixel, +1/+2 apron.  `pairs`: the product EASU kernel resolves rows in
+    // PAIRS (ly, ly + 1), ly even, and evaluates the second pixel of the last pair even when its row lies behind the image (only its store is
+    // guarded): the footprint covers that row too.  (Until round 6 it did not: where the LAST, partial tile row defines the extent -- an image of
+    // a single tile row with an odd height -- the discarded pixel read up to two cell rows past the colour / analysis planes, into the next
+    // plane of the same workgroup.  Found by the fuzz seeds run against the checked build, seed 162312: profiles/r06_bounds.txt.)
+    auto extent = [](uint32_t outN, int tile, float s, float c, bool pairs) {
+        int best = 0;
+        for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
+            uint32_t o1 = o0 + tile - 1 < outN ? o0 + tile - 1 : outN - 1;
+            if (pairs) o1 |= 1u; // the partner row of the last pair (inside the tile: tile heights are even)
+            int f0 = (int)std::floor(mad2((float)o0, s, c)), f1 = (int)std::floor(mad2((float)o1, s, c));
+            best = f1 - f0 + 4 > best ? f1 - f0 + 4 : best;
+        }
+        return best;
+    };
+    p.cellsW = extent(p.outputWidth, kTileW, sx, cx, false);
+    p.cellsH = extent(p.outputHeight, kTileH, sy, cy, true);
+    // fused kernel: EASU runs on the tile plus a 1-pixel ring, origin at pixel (o0 - 1)
+    auto extentRing = [](uint32_t outN, int tile, float s, float c) {
+        int best = 0;
+        for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
+            uint32_t o1 = o0 + tile < outN ? o0 + tile : outN - 1;
+            int f0 = (int)std::floor(mad2((float)o0 - 1.0f, s, c)), f1 = (int)std::floor(mad2((float)o1, s, c));
+            best = f1 - f0 + 4 > best ? f1 - f0 + 4 : best;
+        }
+        return best;
+    };
+    p.fusedCellsW = extentRing(p.outputWidth, kTileW, sx, cx);
+    p.fusedCellsH = extentRing(p.outputHeight, kTileH, sy, cy);
+}
+
+// LDS footprint of one 32x24 NVScaler group
+void nis_footprints(Plan &p)
+{
+    auto extent = [](uint32_t outN, int blk, float s) {
+        int best = 0;
+        for (uint32_t o0 = 0; o0 < outN; o0 += blk) {
+            uint32_t o1 = o0 + blk - 1 < outN ? o0 + blk - 1 : outN - 1;
+            int f0 = (int)std::floor(mad2(0.5f + (float)o0, s, -0.5f)), f1 = (int)std::floor(mad2(0.5f + (float)o1, s, -0.5f));
+            best = f1 - f0 + 7 > best ? f1 - f0 + 7 : best; // 6-tap support (+2/+3) and the edge-map ring (+1)
+        }
+        return best;
+    };
+    p.nisCellsW = extent(p.outputWidth, 32, p.nis.kScaleX);
+    p.nisCellsH = extent(p.outputHeight, 24, p.nis.kScaleY);
+}
+
+// o/outW, o/outH of the bilinear fallback as a multiply and two FMAs: verify against IEEE division for every o
+void reciprocals(Plan &p)
+{
+    auto check = [](uint32_t n, float &rn) {
+        volatile float r = 1.0f / (float)n;
+        rn = r;
+        for (uint32_t o = 0; o < n; ++o) {
+            const float q0 = (float)o * rn;
+            const float rem = std::fma(-q0, (float)n, (float)o);
+            volatile float want = (float)o / (float)n;
+            if (std::fma(rem, rn, q0) != want) return false;
+        }
+        return true;
+    };
+    const bool okW = check(p.outputWidth, p.rcpOut[0]), okH = check(p.outputHeight, p.rcpOut[1]);
+    p.rcpExact = okW && okH;
+}
+
+// column / row taps of the bilinear fallback / NIS DirectCopy (SampleLevel at pos/outSize, 8-bit sub-texel snap): same IEEE
+// operations as fsr_device.inc's bilinear_uv / fixed8, evaluated once per column and row instead of per pixel
+// Layout: [ow column taps | copies of the last column tap up to a multiple of the tile width | oh row taps | 64 spare entries].
+// The staged outside-tile kernel loads the column taps of every pixel QUAD of a 32-wide tile (outside_staged_kernel::issue_taps);
+// the quads on and behind the last column must find VALID taps -- their pixels are never stored, but the taps index the kernel's
+// LDS plane.  (Until round 6 the row taps followed the column taps directly and that quad read row taps as column taps:
+// out-of-plane LDS reads whose values were discarded -- found by the checked build, profiles/r06_bounds.txt.)
+void tap_tables(Plan &p)
+{
+    const uint32_t ow = p.outputWidth, oh = p.outputHeight;
+    std::vector<BilinTap> &taps = p.taps;
+    p.tapYOff = (ow + (uint32_t)kTileW - 1u) & ~((uint32_t)kTileW - 1u);
+    taps.assign((size_t)p.tapYOff + oh + 64, BilinTap{0, 0.0f});
+    auto fill = [](BilinTap *t, uint32_t outN, uint32_t inN) {
+        for (uint32_t o = 0; o < outN; ++o) {
+            volatile float u = (float)o / (float)outN;
+            const float tt = mad2(u, (float)inN, -0.5f);
+            const float s = std::floor(mad2(tt, 256.0f, 0.5f));
+            volatile float q = s * (1.0f / 256.0f);
+            const float f = std::floor(q);
+            t[o].i0 = (int32_t)f;
+            t[o].frac = mad2(f, -256.0f, s) * (1.0f / 256.0f);
+        }
+    };
+    fill(taps.data(), ow, p.inputWidth);
+    for (uint32_t o = ow; o < p.tapYOff; ++o) taps[o] = taps[ow - 1];
+    fill(taps.data() + p.tapYOff, oh, p.inputHeight);
+    // largest [first tap, last tap + 1] span of a tile: the LDS plane of the staged outside-tile kernel
+    auto span = [](const BilinTap *t, uint32_t outN, uint32_t tile) {
+        int best = 2;
+        for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
+            const uint32_t o1 = o0 + tile - 1 < outN ? o0 + tile - 1 : outN - 1;
+            best = std::max(best, t[o1].i0 + 2 - t[o0].i0);
+        }
+        return (uint32_t)best;
+    };
+    p.outsideCols = span(taps.data(), ow, 32);
+    p.outsideRows[0] = span(taps.data() + p.tapYOff, oh, 32);
+    p.outsideRows[1] = span(taps.data() + p.tapYOff, oh, 24);
+}
+
+// Block b of a launch runs on XCD b % 8, each XCD with a private L2: entry b of a work list of n row-major items is item
+// xcd_source(b, n), which hands every XCD a contiguous raster run of the list (the n % 8 trailing entries keep their place).
+inline uint32_t xcd_source(uint32_t b, uint32_t n)
+{
+    const uint32_t full = n & ~7u;
+    return b < full ? (b & 7u) * (full >> 3) + (b >> 3) : b;
+}
+
+// The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one mask group
+// inside the radius (EASU kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel).
+void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH)
+{
+    const uint32_t outW = p.outputWidth, outH = p.outputHeight;
+    const uint32_t tx = (outW + tileW - 1) / tileW, ty = (outH + tileH - 1) / tileH;
+    const uint32_t gpx = tileW / groupW, gpy = tileH / groupH; // mask groups per tile
+    std::vector<uint32_t> &lists = p.lists, &spans = p.spans;
+    std::vector<uint32_t> in[2], outl[2];
+    for (int eye = 0; eye < 2; ++eye) {
+        const uint32_t *c = p.centre[eye];
+        for (uint32_t t = 0; t < tx * ty; ++t) {
+            const uint32_t tyi = t / tx, txi = t - tyi * tx;
+            bool any = false;
+            for (uint32_t g = 0; g < gpx * gpy && !any; ++g) {
+                const uint32_t gx = gpx * txi + (g % gpx), gy = gpy * tyi + (g / gpx);
+                const uint32_t cx = gx * groupW + groupW / 2, cy = gy * groupH + groupH / 2;
+                const uint32_t ax = c[0] - cx, ay = c[1] - cy, bx = c[2] - cx, by = c[3] - cy;
+                any = (ax * ax + ay * ay <= p.radius[1]) || (bx * bx + by * by <= p.radius[1]);
+            }
+            (any ? in[eye] : outl[eye]).push_back(t);
+        }
+    }
+    std::vector<uint32_t> ring[2];
+    for (int eye = 0; eye < 2; ++eye) {
+        std::vector<uint8_t> isIn((size_t)tx * ty, 0);
+        for (uint32_t t : in[eye]) isIn[t] = 1;
+        for (uint32_t t : outl[eye]) {
+            const uint32_t tyi = t / tx, txi = t - tyi * tx;
+            const bool adj = (txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx]);
+            if (adj) ring[eye].push_back(t);
+        }
+    }
+    p.listsShared = in[0] == in[1];
+    // RCAS on the mask-sorted form (RGBA8): per 32-row band, runs of adjacent tiles touching the radius, cut into the DPP
+    // kernel's 62-column segments (rcas_dpp_kernel<.., true>): {x0 | tileY << 16, xEnd}
+    if (tileW == (uint32_t)kTileW && tileH == (uint32_t)kRcasDppTileH && outW < 65536u && ty < 65536u) {
+        for (int eye = 0; eye < 2; ++eye) {
+            p.spanOff[eye] = spans.size() / 2;
+            for (size_t i = 0; i < in[eye].size();) { // in[] is row-major here
+                size_t j = i;
+                while (j + 1 < in[eye].size() && in[eye][j + 1] == in[eye][j] + 1 && (in[eye][j + 1] / tx) == (in[eye][i] / tx)) ++j;
+                const uint32_t tyi = in[eye][i] / tx, xa = (in[eye][i] - tyi * tx) * tileW;
+                const uint32_t xb = std::min((in[eye][j] - tyi * tx + 1) * tileW, outW);
+                for (uint32_t x0 = xa; x0 < xb; x0 += kRcasDppTileW) {
+                    spans.push_back(x0 | (tyi << 16));
+                    spans.push_back(std::min(x0 + (uint32_t)kRcasDppTileW, xb));
+                }
+                i = j + 1;
+            }
+            p.nSpans[eye] = (uint32_t)(spans.size() / 2 - p.spanOff[eye]);
+            // every XCD a contiguous raster run of segments (xcd_source), so that the 128-byte lines two neighbouring
+            // segments share, and the rows two bands share, are fetched once
+            const uint32_t n = p.nSpans[eye];
+            std::vector<uint32_t> r(2 * (size_t)n);
+            for (uint32_t b = 0; b < n; ++b) {
+                const size_t src = p.spanOff[eye] + xcd_source(b, n);
+                r[2 * (size_t)b] = spans[2 * src]; r[2 * (size_t)b + 1] = spans[2 * src + 1];
+            }
+            std::copy(r.begin(), r.end(), spans.begin() + 2 * p.spanOff[eye]);
+        }
+    }
+    auto xcd_order = [](std::vector<uint32_t> &v) {
+        const uint32_t n = (uint32_t)v.size();
+        std::vector<uint32_t> r(n);
+        for (uint32_t b = 0; b < n; ++b) r[b] = v[xcd_source(b, n)];
+        v.swap(r);
+    };
+    for (int eye = 0; eye < 2; ++eye) {
+        xcd_order(in[eye]); xcd_order(outl[eye]);
+        p.nInside[eye] = (uint32_t)in[eye].size(); p.nOutside[eye] = (uint32_t)outl[eye].size();
+        // inside | ring | outside: the ring tiles follow the inside tiles so that ONE EASU launch over nInside + nRing entries
+        // also writes the bilinear intermediate of the ring (its all-outside path), while RCAS walks the first nInside only
+        p.listOffInside[eye] = lists.size(); lists.insert(lists.end(), in[eye].begin(), in[eye].end());
+        p.nRing[eye] = (uint32_t)ring[eye].size();
+        p.listOffRing[eye] = lists.size(); lists.insert(lists.end(), ring[eye].begin(), ring[eye].end());
+        p.listOffOutside[eye] = lists.size(); lists.insert(lists.end(), outl[eye].begin(), outl[eye].end());
+    }
+    // One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin
+    // (first column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of
+    // dependent scalar loads: tile index -> tap tables)
+    p.recs.assign(lists.size() * 4, 0u);
+    const BilinTap *bx = p.taps.data(), *by = p.taps.data() + p.tapYOff;
+    const uint32_t rowsCap = p.outsideRows[tileH == 24 ? 1 : 0];
+    for (size_t i = 0; i < lists.size(); ++i) {
+        const uint32_t t = lists[i], tyi = t / tx, txi = t - tyi * tx;
+        const uint32_t ox0 = txi * tileW, oy0 = tyi * tileH;
+        const int X0 = bx[ox0].i0, Y0 = by[oy0].i0;
+        const int colsN = std::min<int>((int)p.outsideCols, bx[std::min(ox0 + tileW - 1, outW - 1)].i0 + 2 - X0);
+        const int rowsN = std::min<int>((int)rowsCap, by[std::min(oy0 + tileH - 1, outH - 1)].i0 + 2 - Y0);
+        p.recs[4 * i + 0] = ox0 | (oy0 << 16);
+        p.recs[4 * i + 1] = (uint32_t)(X0 + 1) | ((uint32_t)(Y0 + 1) << 16);
+        p.recs[4 * i + 2] = (uint32_t)colsN | ((uint32_t)rowsN << 8);
+    }
+}
+
+// Near-tie guard of a half-float intermediate: the smallest value whose flipped half rounding could exceed the 1e-3 tolerance
+// behind RCAS.  RCAS's gain on its centre tap is at most 1 / (1 - 4 * 0.1875 * sharp) (lobe >= -FSR_RCAS_LIMIT * sharp,
+// ffx_fsr1.h:654,757-765); a half in [b, 2b) moves in steps of b * 2^-10.  Binades whose step times that gain stays under
+// 9e-4 are left alone; +inf (guard off) when no sharpening pass follows the upscale.
+float tie_half_min(const ovrfsr_config &cfg, const Plan &p)
+{
+    if (!(p.doUpscale && p.doSharpen) || cfg.use_nis) return INFINITY;
+    const float gain = 1.0f / (1.0f - 0.75f * con_float(p.rcasCon[0]));
+    float b = 1.0f / 16384.0f; // half's smallest normal binade
+    while (b < 65536.0f && gain * b * (1.0f / 1024.0f) < 9e-4f) b *= 2.0f;
+    return b;
+}
+
+} // namespace
+
+const Refusal *plan_refusals(size_t *count)
+{
+    *count = R_COUNT;
+    return kRefusals;
+}
+
+const char *form_name(Form f)
+{
+    static const char *const names[] = {"none", "upscale only", "sharpen only", "two-pass", "mask-sorted", "fused", "fused with masked outside tiles"};
+    return names[(int)f];
+}
+
+int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint32_t *outW, uint32_t *outH)
+{
+    constexpr uint32_t kMaxExtent = 16384; // same limit CheckImage puts on caller images
+    if (cfg.out_width != 0 && cfg.out_height != 0) {
+        if (cfg.out_width > kMaxExtent || cfg.out_height > kMaxExtent) return OVRFSR_ERR_INVALID_ARGUMENT;
+        *outW = cfg.out_width;
+        *outH = cfg.out_height;
+        return OVRFSR_OK;
+    }
+    // uint32 <- float truncation, PostProcessor.cpp:512-518.  A zero, negative or non-finite scale (a typo in
+    // openvr_mod.cfg) has no defined uint conversion, and a tiny one asks for an unbounded image: both are rejected,
+    // like any size beyond the 16384 texels an image may have here.
+    const float s = cfg.render_scale;
+    if (!std::isfinite(s) || !(s > 0.f)) return OVRFSR_ERR_INVALID_ARGUMENT;
+    const float fw = s < 1.f ? inW / s : inW * s, fh = s < 1.f ? inH / s : inH * s;
+    if (!(fw < (float)(kMaxExtent + 1)) || !(fh < (float)(kMaxExtent + 1))) return OVRFSR_ERR_INVALID_ARGUMENT;
+    *outW = (uint32_t)fw;
+    *outH = (uint32_t)fh;
+    return OVRFSR_OK;
+}
+
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan)
+{
+    Plan p;
+    p.inputWidth = width; p.inputHeight = height; p.inputFormat = format;
+    p.onlyOneEye = onlyOneEye;
+    p.useNis = cfg.use_nis != 0;
+    // what the kernels will see: a multisampled submission is resolved and a BGRA8 one re-ordered to RGBA8 first, R11G11B10F unpacked
+    // (the RGBA16F route from here on): PostProcessor::ApplyPostProcess
+    const uint32_t pf = p.pipelineFormat = pipeline_format(format);
+    // The format of the textures the ctx creates for itself -- the quantised intermediate and the ctx-owned output:
+    //   cfg.reference_formats = 0 (default): the pipeline input's own format.  This library's rule, not the reference's: half-float pipelines
+    //     (BASELINE C5) keep a half intermediate and come back as RGBA16F.  It agrees with the reference for RGBA8, BGRA8 and RGB10A2.
+    //   cfg.reference_formats = 1: the reference's DetermineOutputFormat (PostProcessor.cpp:63-74; upscaledTexture :348, sharpenedTexture :470).
+    p.ownedFormat = cfg.reference_formats ? reference_output_format(pf) : pf;
+    // quantize_intermediate=0 keeps fp32, whatever the format rule.
+    const uint32_t mid = p.intermediateFormat = cfg.quantize_intermediate ? p.ownedFormat : (uint32_t)OVRFSR_FORMAT_RGBA32F;
+    uint32_t ow = 0, oh = 0;
+    if (plan_output_size(cfg, width, height, &ow, &oh) != OVRFSR_OK || ow == 0 || oh == 0) return kRefusals[R_OUTPUT_SIZE];
+    p.outputWidth = ow; p.outputHeight = oh;
+
+    const bool explicitSize = cfg.out_width != 0 && cfg.out_height != 0;
+    const bool scaleNotOne = explicitSize ? (ow != width || oh != height) : (cfg.render_scale != 1.f);
+    p.doUpscale = cfg.fsr_enabled && scaleNotOne;                       // :586
+    p.doSharpen = cfg.fsr_enabled && (!cfg.use_nis || !scaleNotOne);    // :591
+    if (cfg.stage_mask == 1) p.doSharpen = false;                       // "EASU-only" (BASELINE C1)
+    if (cfg.stage_mask == 2) p.doUpscale = false;
+    if (cfg.stage_mask < 0 || cfg.stage_mask > 2) return kRefusals[R_STAGE_MASK];
+    if (!p.doUpscale && (ow != width || oh != height)) return kRefusals[R_SHARPEN_ONLY_SIZE];
+    if (cfg.precision != OVRFSR_PRECISION_FP32 && cfg.precision != OVRFSR_PRECISION_FP32_STRICT && cfg.precision != OVRFSR_PRECISION_FP32_EXACT)
+        return kRefusals[R_PRECISION];
+    const bool exact = cfg.precision == OVRFSR_PRECISION_FP32_EXACT, both = p.doUpscale && p.doSharpen;
+    p.rcasPrec = cfg.precision;
+    p.launchPrec = exact ? (int)PREC_FP32 : cfg.precision;
+    if (exact) {
+        if (cfg.use_nis) return kRefusals[R_EXACT_NIS];
+        if (cfg.fused == 1) return kRefusals[R_EXACT_FUSED_ASKED];
+        if (both && !cfg.quantize_intermediate) return kRefusals[R_EXACT_FLOAT_MID];
+        if (p.doSharpen && (p.doUpscale ? mid : pf) != OVRFSR_FORMAT_RGBA8_UNORM) return kRefusals[R_EXACT_SOURCE];
+    }
+
+    for (int eye = 0; eye < 2; ++eye) {
+        mask_constants(p.centre[eye], p.radius, ow, oh, cfg.proj_centre, cfg.radius, onlyOneEye ? 1 : 0, eye);
+        const uint32_t gw = cfg.use_nis ? 32u : 16u, gh = cfg.use_nis ? (scaleNotOne ? 24u : 32u) : 16u;
+        p.maskMode[eye] = classify_mask(p.centre[eye], p.radius[1], ow, oh, gw, gh);
+    }
+    if (cfg.use_nis) {
+        // NVScalerUpdateConfig (scale != 1) or NVSharpenUpdateConfig (out == in), PostProcessor.cpp:308,:433
+        if (!nis_scaler_config(&p.nis, cfg.sharpness, width, height, ow, oh)) return kRefusals[R_NIS_SCALE];
+        p.nis.reserved1 = cfg.debug_mode ? 1.f : 0.f; // :309
+        if (p.doUpscale) {
+            nis_footprints(p);
+            if (nis_pitch(p.nisCellsW) == 0 || nis_scaler_lds_bytes(p.nisCellsW, p.nisCellsH) > 64 * 1024) return kRefusals[R_NIS_LDS];
+        }
+    } else if (p.doUpscale) {
+        easu_footprints(p);
+        if (easu_lds_bytes(p.launchPrec, (int)pf, p.cellsW, p.cellsH) > 64 * 1024) return kRefusals[R_EASU_LDS];
+    }
+    reciprocals(p);
+    if (p.doUpscale) tap_tables(p);
+    p.tileLists = p.doUpscale && p.launchPrec == PREC_FP32 && (p.maskMode[0] == MASK_MIXED || p.maskMode[1] == MASK_MIXED);
+    if (p.tileLists) {
+        // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
+        if (cfg.use_nis) tile_lists(p, 32, 24, 32, 24);
+        else tile_lists(p, kTileW, kTileH, 16, 16);
+    }
+    if (p.doSharpen && !cfg.use_nis) {
+        float s = cfg.sharpness;
+        s = s < 1.0f ? s : 1.0f; // AClampF1(x,0,1) = max(0,min(x,1)), PostProcessor.cpp:420
+        s = s > 0.0f ? s : 0.0f;
+        rcas_con(p.rcasCon, 2.f - 2 * s);
+        p.rcasCon[3] = cfg.debug_mode ? 1u : 0u; // :430
+    }
+    p.tieHalfMin = tie_half_min(cfg, p);
+
+    // The form.  One launch with the intermediate in LDS only on request: on this chip both stages are VALU-bound and the ring
+    // recompute costs more than the HBM round trip saves, so auto (-1) means two kernels.
+    // auto: masked product-build pipelines run fused + mask-sorted (most of their pixels are plain bilinear copies, and tiles outside the
+    // radius need no intermediate at all); unmasked ones stay two-pass (VALU-bound, the ring recompute costs 9 %)
+    const bool tenBit = pf == OVRFSR_FORMAT_RGB10A2_UNORM; // two-kernel pipeline only (header)
+    if (tenBit && cfg.fused == 1) return kRefusals[R_FUSED_TEN_BIT];
+    // cfg.reference_formats with a float pipeline input (R11G11B10F counts as RGBA16F here): the intermediate is UNORM8, and no fused kernel is
+    // built for a byte intermediate of a float source -- two-kernel forms only, the mask-sorted one where there is a mask
+    const bool floatIn = pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F;
+    if (cfg.reference_formats && floatIn && cfg.fused == 1) return kRefusals[R_FUSED_FLOAT_REFERENCE];
+    const bool byteMidOfFloat = floatIn && mid == OVRFSR_FORMAT_RGBA8_UNORM;
+    const bool fusedFits = fused_lds_bytes(p.launchPrec, (int)pf, (int)mid, p.fusedCellsW, p.fusedCellsH) <= kFusedLdsMax;
+    const bool autoFused = !tenBit && !byteMidOfFloat && cfg.fused == -1 && p.tileLists && p.fusedCellsW <= 40 && fusedFits;
+    // auto on a masked product-build EASU+RCAS pipeline: the two-pass kernels on the tiles touching the radius, tiles
+    // outside written in final form (ApplySorted); cfg.fused = 1 keeps the single fused kernel on those tiles
+    // Measured: with 4-byte pixels the sorted two-pass form wins (C2 shape, radius 0.5: +13 %); with 8/16-byte
+    // pixels the outside kernel dominates the frame, and the three dependent launches of the sorted form lose to the
+    // fused kernel (C5: -15 %), so those keep it.  The condition is the INTERMEDIATE's format: under cfg.reference_formats a float source
+    // has a UNORM8 intermediate too, and takes this form (RCAS on rcas_dpp_kernel's span records; profiles/reference_formats.txt).
+    const bool sorted = cfg.fused == -1 && p.tileLists && both && !cfg.use_nis && (pf == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) &&
+                        mid == OVRFSR_FORMAT_RGBA8_UNORM;
+    bool fused = false;
+    if ((cfg.fused == 1 || (autoFused && !sorted)) && both && !cfg.use_nis) {
+        const bool pitchOk = p.launchPrec == PREC_FP32_STRICT || p.fusedCellsW <= 40;
+        if (!pitchOk || !fusedFits) return kRefusals[R_FUSED_LDS];
+        fused = true;
+    }
+    if (fused && exact) return kRefusals[R_EXACT_FUSED]; // (fused = -1 picks it for half / float intermediates only, refused above)
+    p.form = sorted ? Form::MaskSorted : fused ? (p.tileLists ? Form::FusedMaskedOutside : Form::Fused)
+           : both ? Form::TwoPass : p.doUpscale ? Form::UpscaleOnly : p.doSharpen ? Form::SharpenOnly : Form::None;
+
+    // The tiles outside the radius of a masked pass are independent of the tiles touching it: their kernel can run on the ctx's auxiliary
+    // stream beside the main kernel.  It does where it is the per-pixel, latency-bound kernel (half / float sources, minification); the
+    // LDS-staged one of RGBA8 sources (outside_staged_ok) streams at HBM speed and is faster in order (measurements: PostProcessor::Fork).
+    // cfg.reference_formats: the mask-sorted form of a float source (UNORM8 intermediate) runs in order on the caller's stream too, as the
+    // RGBA8 one does -- its three launches are short, and the fork / join pair costs ~10 us per cross-queue wait
+    BatchView v{};
+    v.inW = (int32_t)width; v.inH = (int32_t)height; v.outW = (int32_t)ow; v.outH = (int32_t)oh;
+    p.overlapOutside = p.tileLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
+    *plan = std::move(p);
+    return Refusal{};
+}
+
+Refusal destination_refusal(const Plan &plan, uint32_t destFormat)
+{
+    // exact stores: the sharpen stage's destination must be RGBA8 too (a BGRA8 destination is refused below in every mode)
+    if (plan.rcasPrec == OVRFSR_PRECISION_FP32_EXACT && plan.doSharpen && destFormat != OVRFSR_FORMAT_RGBA8_UNORM && destFormat != OVRFSR_FORMAT_BGRA8_UNORM)
+        return kRefusals[R_DEST_EXACT];
+    if (input_only(destFormat)) return kRefusals[R_DEST_INPUT_ONLY]; // (BGRA8: see the table)
+    // R10G10B10A2 exists for the reference's 10-bit path: 10-bit in -> 10-bit out (or float, to measure parity)
+    const bool inTen = plan.pipelineFormat == OVRFSR_FORMAT_RGB10A2_UNORM, outTen = destFormat == OVRFSR_FORMAT_RGB10A2_UNORM;
+    if ((outTen && !inTen) || (inTen && !outTen && destFormat != OVRFSR_FORMAT_RGBA32F)) return kRefusals[R_DEST_TEN_BIT_PAIR];
+    // (a float intermediate in front of a 10-bit destination is a kernel pair nobody builds: refused before anything is launched,
+    // instead of surfacing as a launch error behind the EASU pass -- found by the round-6 format sweep)
+    if (outTen && plan.doUpscale && plan.doSharpen && plan.intermediateFormat != OVRFSR_FORMAT_RGB10A2_UNORM) return kRefusals[R_DEST_TEN_BIT_MID];
+    return Refusal{};
+}
+
+// 4-sample RGBA8 on C2's path -- product build, unmasked easu_fast_kernel, two-kernel pipeline with a UNORM8 intermediate or EASU-only into
+// UNORM8 -- is resolved inside EASU's staging sweep (FMT_RGBA8_MS4, the same resolve_unorm8 the resolve pass runs: identical staged bytes,
+// identical output); every other multisampled input takes the resolve pass.  -DOVRFSR_MSAA_RESOLVE_PASS (measurement build, never shipped)
+// sends this path through the resolve pass too: the A/B of profiles/msaa_c2.txt.
+bool resolve_in_staging(const Plan &plan, uint32_t destFormat)
+{
+#ifdef OVRFSR_MSAA_RESOLVE_PASS
+    (void)plan; (void)destFormat;
+    return false;
+#else
+    const bool unmasked = !plan.tileLists && plan.maskMode[0] == MASK_ALL_INSIDE && plan.maskMode[1] == MASK_ALL_INSIDE;
+    const bool plain = plan.form == Form::UpscaleOnly || plan.form == Form::TwoPass;
+    const uint32_t easuOut = plan.doSharpen ? plan.intermediateFormat : destFormat;
+    return plan.inputFormat == (uint32_t)FMT_RGBA8_MS4 && plain && !plan.useNis && unmasked &&
+           easu_msaa_fused_ok(plan.launchPrec, (int)easuOut, plan.cellsW);
+#endif
+}
+
+} // namespace ovrfsr

@@ -1,0 +1,98 @@
+// pipeline_plan.h -- what the launch manager will do for one (configuration, submitted format, size), decided on the host before anything is
+// built on the device.  plan_pipeline() is pure: no HIP call, no device, no state -- footprints, mask classification, tile lists, LDS fit and
+// every refusal are host arithmetic.  PostProcessor (postprocessor.cpp) plans, then uploads what the Plan holds; tests/debug/plan_probe.cpp
+// runs the planner alone, under the host sanitizers.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/openvr_fsr_amd.h"
+#include "fsr_params.h"
+#include "nis_tables.h"
+
+namespace ovrfsr {
+
+// host-side constant math (restates FsrEasuCon / FsrRcasCon / NVScalerUpdateConfig; see constants.cpp)
+void easu_con(uint32_t con[16], float inVpW, float inVpH, float inW, float inH, float outW, float outH);
+void rcas_con(uint32_t con[4], float stops);
+void mask_constants(uint32_t centre[4], uint32_t radius[4], uint32_t outW, uint32_t outH, const float proj[4],
+                    float cfgRadius, int onlyOneEye, int eye);
+uint32_t classify_mask(const uint32_t centre[4], uint32_t r2, uint32_t outW, uint32_t outH, uint32_t gw, uint32_t gh);
+
+// The launches of one apply, by the names the documents use ("Plan, then upload")
+enum class Form {
+    None,              // no stage selected: the submission is handed back untouched
+    UpscaleOnly,       // EASU or NVScaler into the destination
+    SharpenOnly,       // RCAS or NVSharpen (output size == input size)
+    TwoPass,           // upscale into the intermediate, sharpen into the destination
+    MaskSorted,        // masked EASU+RCAS: both passes on the tiles touching the radius, outside tiles written in final form (ApplySorted)
+    Fused,             // one kernel, the intermediate in LDS
+    FusedMaskedOutside // the fused kernel on the tiles touching the radius, outside tiles written in final form
+};
+const char *form_name(Form f); // for tests/debug/plan_probe.cpp: the library itself never prints a form
+
+// OVRFSR_OK, or why the call is refused.  `disables`: refused like a failed build -- the ctx stays disabled until reset.
+struct Refusal {
+    int status = OVRFSR_OK;
+    const char *text = "";
+    bool disables = false;
+    explicit operator bool() const { return status != OVRFSR_OK; }
+};
+// every refusal plan_pipeline and destination_refusal can produce, and nothing else they return.  Listed for tests/debug/plan_probe.cpp
+// (tests/test_pipeline_plan.py holds the same list); the library does not call it.
+const Refusal *plan_refusals(size_t *count);
+
+struct Plan {
+    // what was planned for: the canonical submitted format (a multisampled encoding included), its size, one eye per texture or both
+    uint32_t inputWidth = 0, inputHeight = 0, inputFormat = 0;
+    bool onlyOneEye = true;
+    uint32_t outputWidth = 0, outputHeight = 0;
+    // stage selection, PostProcessor.cpp:530-535 / :586-594
+    bool doUpscale = false, doSharpen = false;
+    bool useNis = false;         // NVScaler / NVSharpen in place of EASU / RCAS
+    Form form = Form::None;
+    bool tileLists = false;      // masked launches walk the per-eye tile lists below (product arithmetic, an upscale stage, a mixed mask)
+    bool overlapOutside = false; // ... and their outside-tile kernel runs on the ctx's auxiliary stream (see PostProcessor::Fork)
+    // pipeline: what the kernels see in the submission's place; intermediate: the upscale stage's destination in front of a sharpen stage;
+    // owned: the textures the ctx creates for itself (cfg.reference_formats)
+    uint32_t pipelineFormat = 0, intermediateFormat = 0, ownedFormat = 0;
+    // OVRFSR_PRECISION_FP32_EXACT is the product build everywhere but in RCAS: every launcher and size rule sees launchPrec, launch_rcas rcasPrec
+    int launchPrec = PREC_FP32, rcasPrec = PREC_FP32;
+    // "constant buffers", one per eye: PostProcessor.cpp:296-338, :419-460
+    uint32_t easuCon[16] = {};
+    uint32_t rcasCon[4] = {};
+    NisConstants nis = {};       // the 256-byte NISConfig (PostProcessor.cpp:307-310)
+    uint32_t centre[2][4] = {};
+    uint32_t radius[4] = {};
+    uint32_t maskMode[2] = {};
+    float tieHalfMin = 0.0f;     // near-tie guard of a half intermediate (plan_pipeline); +inf = off
+    int cellsW = 0, cellsH = 0;           // LDS footprint of one EASU tile
+    int fusedCellsW = 0, fusedCellsH = 0; // ... of the 34x34 EASU block of the fused kernel
+    int nisCellsW = 0, nisCellsH = 0;     // ... of one 32x24 NVScaler group
+    float rcpOut[2] = {0, 0};    // RN(1/outW), RN(1/outH) and whether mul+2fma reproduces o/out for every o (div_exact)
+    bool rcpExact = false;
+    // bilinear fallback / DirectCopy taps: [outW column taps, padded to a multiple of the tile width with copies of the last | outH row taps
+    // at tapYOff | 64 spare entries]
+    std::vector<BilinTap> taps;
+    uint32_t tapYOff = 0;
+    uint32_t outsideCols = 0, outsideRows[2] = {0, 0}; // bilinear footprint bound of a 32-wide tile; rows for 32- and 24-row tiles
+    // mask-sorted tile lists, per eye: inside | ring | outside (ring: outside tiles 4-adjacent to an inside tile); one 4-dword record per
+    // list entry (OutsideArgs::tileRec); RCAS segments of the inside runs, 2 dwords each (RcasArgs::spanRec)
+    std::vector<uint32_t> lists, recs, spans; // (PostProcessor frees these three once they are uploaded; the counts and offsets stay)
+    uint32_t nInside[2] = {0, 0}, nOutside[2] = {0, 0}, nRing[2] = {0, 0}, nSpans[2] = {0, 0};
+    size_t listOffInside[2] = {0, 0}, listOffOutside[2] = {0, 0}, listOffRing[2] = {0, 0}, spanOff[2] = {0, 0}; // spanOff in segments
+    bool listsShared = false;    // both eyes have identical lists
+};
+
+// ovrfsr_output_size behind its argument checks
+int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint32_t *outW, uint32_t *outH);
+
+// `format`: canonical (a single-sample encoding reduced to its base format).  On a refusal *plan is left as it was.
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan);
+
+// what depends on the destination the call names
+Refusal destination_refusal(const Plan &plan, uint32_t destFormat);
+// a 4-sample RGBA8 submission resolved inside EASU's staging sweep instead of the resolve pass
+bool resolve_in_staging(const Plan &plan, uint32_t destFormat);
+
+} // namespace ovrfsr

@@ -1,7 +1,6 @@
 // postprocessor.cpp -- see postprocessor.hpp.  Reference: src/postprocess/PostProcessor.cpp.
 #include "postprocessor.hpp"
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,13 +66,6 @@ static const char *const kCaptureRefusal = "this call has to build device resour
 template <class T>
 static inline T *at_offset(T *p, size_t off) { return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + off); }
 
-// a*b+c with two roundings, identical to the kernels' mad_unfused (separate statements)
-static inline float mad2(float a, float b, float c)
-{
-    volatile float t = a * b;
-    return t + c;
-}
-
 void DeviceBuffer::release()
 {
     if (p) (void)hipFree(p);
@@ -93,7 +85,7 @@ PostProcessor::PostProcessor(int device, const ovrfsr_config &cfg) : device_(dev
 //     latency-bound; round 3 rebuilt it.)
 //   * other sources (easu_outside_kernel / nis_outside_kernel: per-pixel, latency-bound, 8 workgroups per CU of spare issue slots
 //     beside the fused kernel's 3): YES -- C5 13.9 k against 10.3 k pairs/s at 128 images per call, 12.8 k against 10.6 k at 2.
-// `overlap` is that decision (OverlapOutside).  -DOVRFSR_SERIAL (measurement build) launches everything in order on the caller's
+// `overlap` is that decision (Plan::overlapOutside).  -DOVRFSR_SERIAL (measurement build) launches everything in order on the caller's
 // stream, for stand-alone kernel timings (tools/debug/kt.sh, tools/debug/serial_vs_overlap.sh).
 hipStream_t PostProcessor::Fork(hipStream_t user, bool overlap)
 {
@@ -146,16 +138,6 @@ PostProcessor::~PostProcessor()
     }
 }
 
-bool PostProcessor::OverlapOutside(const ovrfsr_image &in) const
-{
-    // launch_easu_outside / launch_nis_outside take the LDS-staged kernel for RGBA8 sources when upscaling (outside_staged_ok)
-    const bool staged = in.format == OVRFSR_FORMAT_RGBA8_UNORM && in.width <= outputWidth_ && in.height <= outputHeight_;
-    // cfg.reference_formats: the mask-sorted form of a float source (UNORM8 intermediate) runs in order on the caller's stream, as the
-    // RGBA8 one does -- its three launches are short, and the fork / join pair costs ~10 us per cross-queue wait
-    if (useSorted_ && in.format != OVRFSR_FORMAT_RGBA8_UNORM) return false;
-    return !staged;
-}
-
 int PostProcessor::Fail(int status, const std::string &what)
 {
     lastError_ = what;
@@ -174,19 +156,13 @@ void PostProcessor::ResetKeeping(bool keepRetired)
     if (!keepRetired) { pairFirstEye_ = -1; pairDefer_ = true; lastEye_ = -1; } // an explicit reset forgets the learned submission order
     enabled_ = true;
     initialized_ = false;
+    plan_ = Plan{};             // nothing of a previous configuration survives: the next apply plans afresh
     for (DeviceBuffer *b : {&swizzled_, &resolved_, &upscaled_, &sharpened_}) b->release();
-    if (nisCoefDev_) (void)hipFree(nisCoefDev_);
-    if (bilinDev_) (void)hipFree(bilinDev_);
-    if (tileListDev_) (void)hipFree(tileListDev_);
-    tileListDev_ = nullptr;
-    tileRecDev_ = nullptr;
-    spanRecDev_ = nullptr;
-    nSpans_[0] = nSpans_[1] = 0;
-    nInside_[0] = nInside_[1] = nOutside_[0] = nOutside_[1] = nRing_[0] = nRing_[1] = 0;
+    for (void *t : {(void *)nisCoefDev_, (void *)bilinDev_, (void *)tileListDev_})
+        if (t) (void)hipFree(t);
     nisCoefDev_ = nullptr;
     bilinDev_ = nullptr;
-    bilinHost_.clear(); // never let taps of a previous configuration reach PrepareTileLists' footprint records
-    bilYOff_ = 0;
+    tileListDev_ = tileRecDev_ = spanRecDev_ = nullptr;
     lastSubmittedTexture_ = nullptr;
     outputTexture_ = ovrfsr_image{};
     eyeCount_ = 0;
@@ -235,239 +211,63 @@ int PostProcessor::EnsureBuffer(DeviceBuffer &buf, size_t need)
     return OVRFSR_OK;
 }
 
-// OVRFSR_PRECISION_FP32_EXACT is the product build everywhere but in RCAS: every launcher and size rule except launch_rcas sees PREC_FP32
-int PostProcessor::LaunchPrec() const { return cfg_.precision == OVRFSR_PRECISION_FP32_EXACT ? (int)PREC_FP32 : cfg_.precision; }
-bool PostProcessor::ProductArithmetic() const { return LaunchPrec() == PREC_FP32; }
-
-// exact stores: the sharpen stage's destination must be RGBA8 too.  Known only once the call names its `out`; refused like a failed build
-int PostProcessor::CheckExactDestination(uint32_t format)
+// The destination refusals that count as a failed build (exact stores: the sharpen stage's destination must be RGBA8 too): known only once
+// the call names its `out`, they disable the ctx.  The others (destination_refusal) are ApplyPostProcess's: a pair_submit first eye is
+// recorded with such a destination and refused when it is launched.
+int PostProcessor::RefuseDisablingDestination(uint32_t format)
 {
-    if (cfg_.precision != OVRFSR_PRECISION_FP32_EXACT || !doSharpen_ || format == OVRFSR_FORMAT_RGBA8_UNORM || format == OVRFSR_FORMAT_BGRA8_UNORM)
-        return OVRFSR_OK; // (a BGRA8 destination is refused by ApplyPostProcess in every mode)
+    const Refusal refused = destination_refusal(plan_, format);
+    if (!refused || !refused.disables) return OVRFSR_OK;
     enabled_ = false;
-    return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must write RGBA8 (a half, float or 10-bit destination promises no exact bytes)");
-}
-
-uint32_t PostProcessor::IntermediateFormat() const
-{
-    // quantize_intermediate=0 keeps fp32, whatever the format rule.
-    if (!cfg_.quantize_intermediate) return OVRFSR_FORMAT_RGBA32F;
-    return OwnedFormat(inputFormat_);
-}
-
-// The format of the textures the ctx creates for itself -- the quantised intermediate and the ctx-owned output -- for a submission of
-// format `submitted` (a multisampled encoding included: what the pipeline sees in its place decides).
-//   cfg.reference_formats = 0 (default): the pipeline input's own format.  This library's rule, not the reference's: half-float pipelines
-//     (BASELINE C5) keep a half intermediate and come back as RGBA16F.  It agrees with the reference for RGBA8, BGRA8 and RGB10A2.
-//   cfg.reference_formats = 1: the reference's DetermineOutputFormat (PostProcessor.cpp:63-74; upscaledTexture :348, sharpenedTexture :470).
-uint32_t PostProcessor::OwnedFormat(uint32_t submitted) const
-{
-    const uint32_t f = pipeline_format(submitted);
-    return cfg_.reference_formats ? reference_output_format(f) : f;
+    return Fail(refused.status, refused.text);
 }
 
 // the upscale stage's destination where a sharpening stage follows: n images of the output size, tight pitch, in upscaled_
 int PostProcessor::IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride)
 {
-    mid->width = outputWidth_; mid->height = outputHeight_;
-    mid->format = IntermediateFormat();
-    mid->pitch_bytes = outputWidth_ * texel_bytes(mid->format);
-    *midStride = (size_t)mid->pitch_bytes * outputHeight_;
+    mid->width = plan_.outputWidth; mid->height = plan_.outputHeight;
+    mid->format = plan_.intermediateFormat;
+    mid->pitch_bytes = plan_.outputWidth * texel_bytes(mid->format);
+    *midStride = (size_t)mid->pitch_bytes * plan_.outputHeight;
     int rc = EnsureBuffer(upscaled_, *midStride * n);
     mid->data = upscaled_.p;
     return rc;
 }
 
-void PostProcessor::PrepareUpscalingResources()
+// Plan, then upload: everything that decides the pipeline -- and every refusal -- is host arithmetic (pipeline_plan.cpp), so a refused
+// configuration allocates nothing.  What the plan holds is then created on the device, in a fixed order (fault injection counts creations).
+int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneEye)
 {
-    easu_con(easuCon_, (float)inputWidth_, (float)inputHeight_, (float)inputWidth_, (float)inputHeight_,
-             (float)outputWidth_, (float)outputHeight_);
-    float sx, sy, cx, cy;
-    std::memcpy(&sx, &easuCon_[0], 4); std::memcpy(&sy, &easuCon_[1], 4);
-    std::memcpy(&cx, &easuCon_[2], 4); std::memcpy(&cy, &easuCon_[3], 4);
-    // LDS footprint of one 32x32 output tile: f-texel of first and last pixel, +1/+2 apron.  `pairs`: the product EASU kernel resolves rows in
-    // PAIRS (ly, ly + 1), ly even, and evaluates the second pixel of the last pair even when its row lies behind the image (only its store is
-    // guarded): the footprint covers that row too.  (Until round 6 it did not: where the LAST, partial tile row defines the extent -- an image of
-    // a single tile row with an odd height -- the discarded pixel read up to two cell rows past the colour / analysis planes, into the next
-    // plane of the same workgroup.  Found by the fuzz seeds run against the checked build, seed 162312: profiles/r06_bounds.txt.)
-    auto extent = [](uint32_t outN, int tile, float s, float c, bool pairs) {
-        int best = 0;
-        for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
-            uint32_t o1 = o0 + tile - 1 < outN ? o0 + tile - 1 : outN - 1;
-            if (pairs) o1 |= 1u; // the partner row of the last pair (inside the tile: tile heights are even)
-            int f0 = (int)std::floor(mad2((float)o0, s, c)), f1 = (int)std::floor(mad2((float)o1, s, c));
-            best = f1 - f0 + 4 > best ? f1 - f0 + 4 : best;
-        }
-        return best;
-    };
-    cellsW_ = extent(outputWidth_, kTileW, sx, cx, false);
-    cellsH_ = extent(outputHeight_, kTileH, sy, cy, true);
-    // fused kernel: EASU runs on the tile plus a 1-pixel ring, origin at pixel (o0 - 1)
-    auto extentRing = [](uint32_t outN, int tile, float s, float c) {
-        int best = 0;
-        for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
-            uint32_t o1 = o0 + tile < outN ? o0 + tile : outN - 1;
-            int f0 = (int)std::floor(mad2((float)o0 - 1.0f, s, c)), f1 = (int)std::floor(mad2((float)o1, s, c));
-            best = f1 - f0 + 4 > best ? f1 - f0 + 4 : best;
-        }
-        return best;
-    };
-    fusedCellsW_ = extentRing(outputWidth_, kTileW, sx, cx);
-    fusedCellsH_ = extentRing(outputHeight_, kTileH, sy, cy);
-}
-
-void PostProcessor::PrepareSharpeningResources()
-{
-    float s = cfg_.sharpness;
-    s = s < 1.0f ? s : 1.0f; // AClampF1(x,0,1) = max(0,min(x,1)), PostProcessor.cpp:420
-    s = s > 0.0f ? s : 0.0f;
-    rcas_con(rcasCon_, 2.f - 2 * s);
-    rcasCon_[3] = cfg_.debug_mode ? 1u : 0u; // :430
-}
-
-int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
-{
-    inputWidth_ = submitted.width;
-    inputHeight_ = submitted.height;
-    inputFormat_ = submitted.format;
-    ovrfsr_image in = submitted; // what the kernels will see: a multisampled submission is resolved and a BGRA8 one re-ordered to RGBA8 first,
-    in.format = pipeline_format(in.format); // R11G11B10F unpacked (the RGBA16F route from here on): ApplyPostProcess
-    uint32_t ow = 0, oh = 0;
-    if (ovrfsr_output_size(&cfg_, in.width, in.height, &ow, &oh) != OVRFSR_OK || ow == 0 || oh == 0)
-        return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "output size is zero or beyond 16384 texels (render_scale must be finite and > 0)");
-    outputWidth_ = ow;
-    outputHeight_ = oh;
-
-    const bool explicitSize = cfg_.out_width != 0 && cfg_.out_height != 0;
-    const bool scaleNotOne = explicitSize ? (ow != in.width || oh != in.height) : (cfg_.render_scale != 1.f);
-    doUpscale_ = cfg_.fsr_enabled && scaleNotOne;                       // :586
-    doSharpen_ = cfg_.fsr_enabled && (!cfg_.use_nis || !scaleNotOne);   // :591
-    if (cfg_.stage_mask == 1) doSharpen_ = false;                       // "EASU-only" (BASELINE C1)
-    if (cfg_.stage_mask == 2) doUpscale_ = false;
-    if (cfg_.stage_mask < 0 || cfg_.stage_mask > 2) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "bad stage_mask");
-    if (!doUpscale_ && (ow != in.width || oh != in.height))
-        return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "sharpen-only needs output size == input size");
-    if (cfg_.precision != OVRFSR_PRECISION_FP32 && cfg_.precision != OVRFSR_PRECISION_FP32_STRICT && cfg_.precision != OVRFSR_PRECISION_FP32_EXACT)
-        return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "unknown precision");
-    if (cfg_.precision == OVRFSR_PRECISION_FP32_EXACT) {
-        // exact stores (header): promised where the sharpen stage is RCAS from RGBA8 to RGBA8 behind a quantised intermediate; every other
-        // configuration with a sharpen stage is refused -- nothing in it promises the strict build's bytes, so the mode must not pretend to
-        if (cfg_.use_nis) return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: NIS has no exact-stores form (use_nis)");
-        if (cfg_.fused == 1) return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form (fused = 1)");
-        if (doUpscale_ && doSharpen_ && !cfg_.quantize_intermediate)
-            return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read a UNORM8 intermediate (quantize_intermediate = 0)");
-        if (doSharpen_ && (doUpscale_ ? IntermediateFormat() : in.format) != OVRFSR_FORMAT_RGBA8_UNORM)
-            return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: RCAS must read RGBA8 (a half, float or 10-bit intermediate or input promises no exact bytes)");
+    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_);
+    if (refused) return Fail(refused.status, refused.text);
+    if (plan_.useNis) { // coef_scale[512] | coef_usm[512], PostProcessor.cpp:366-382
+        hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(nisCoefDev_, nis_coef_scale(), 512 * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(nisCoefDev_ + 512, nis_coef_usm(), 512 * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("NIS coefficient upload: ") + hipGetErrorString(e));
     }
-
-    for (int eye = 0; eye < 2; ++eye) {
-        mask_constants(centre_[eye], radius_, ow, oh, cfg_.proj_centre, cfg_.radius, textureContainsOnlyOneEye_ ? 1 : 0, eye);
-        const uint32_t gw = cfg_.use_nis ? 32u : 16u, gh = cfg_.use_nis ? (scaleNotOne ? 24u : 32u) : 16u;
-        maskMode_[eye] = classify_mask(centre_[eye], radius_[1], ow, oh, gw, gh);
-    }
-    if (cfg_.use_nis) {
-        int rc = PrepareNisResources();
-        if (rc != OVRFSR_OK) return rc;
-    } else if (doUpscale_) {
-        PrepareUpscalingResources();
-        const size_t lds = easu_lds_bytes(LaunchPrec(), (int)in.format, cellsW_, cellsH_);
-        if (lds > 64 * 1024) return Fail(OVRFSR_ERR_UNSUPPORTED, "scale ratio needs more LDS than one tile may use");
-    }
-    {
-        // o/outW, o/outH of the bilinear fallback as a multiply and two FMAs: verify against IEEE division for every o
-        auto check = [](uint32_t n, float &rn) {
-            volatile float r = 1.0f / (float)n;
-            rn = r;
-            for (uint32_t o = 0; o < n; ++o) {
-                const float q0 = (float)o * rn;
-                const float rem = std::fma(-q0, (float)n, (float)o);
-                volatile float want = (float)o / (float)n;
-                if (std::fma(rem, rn, q0) != want) return false;
-            }
-            return true;
-        };
-        const bool okW = check(ow, rcpOut_[0]), okH = check(oh, rcpOut_[1]);
-        rcpExact_ = okW && okH;
-    }
-    if (doUpscale_) {
-        // column / row taps of the bilinear fallback / NIS DirectCopy (SampleLevel at pos/outSize, 8-bit sub-texel snap): same IEEE
-        // operations as fsr_device.inc's bilinear_uv / fixed8, evaluated once per column and row instead of per pixel
-        // Layout: [ow column taps | copies of the last column tap up to a multiple of the tile width | oh row taps | 64 spare entries].
-        // The staged outside-tile kernel loads the column taps of every pixel QUAD of a 32-wide tile (outside_staged_kernel::issue_taps);
-        // the quads on and behind the last column must find VALID taps -- their pixels are never stored, but the taps index the kernel's
-        // LDS plane.  (Until round 6
-        // the row taps followed the column taps directly and that quad read row taps as column taps: out-of-plane LDS reads whose values
-        // were discarded -- found by the checked build, profiles/r06_bounds.txt.)
-        std::vector<BilinTap> &taps = bilinHost_;
-        bilYOff_ = (ow + (uint32_t)kTileW - 1u) & ~((uint32_t)kTileW - 1u);
-        taps.assign((size_t)bilYOff_ + oh + 64, BilinTap{0, 0.0f});
-        auto fill = [](BilinTap *t, uint32_t outN, uint32_t inN) {
-            for (uint32_t o = 0; o < outN; ++o) {
-                volatile float u = (float)o / (float)outN;
-                const float tt = mad2(u, (float)inN, -0.5f);
-                const float s = std::floor(mad2(tt, 256.0f, 0.5f));
-                volatile float q = s * (1.0f / 256.0f);
-                const float f = std::floor(q);
-                t[o].i0 = (int32_t)f;
-                t[o].frac = mad2(f, -256.0f, s) * (1.0f / 256.0f);
-            }
-        };
-        fill(taps.data(), ow, in.width);
-        for (uint32_t o = ow; o < bilYOff_; ++o) taps[o] = taps[ow - 1];
-        fill(taps.data() + bilYOff_, oh, in.height);
-        // largest [first tap, last tap + 1] span of a tile: the LDS plane of the staged outside-tile kernel
-        auto span = [](const BilinTap *t, uint32_t outN, uint32_t tile) {
-            int best = 2;
-            for (uint32_t o0 = 0; o0 < outN; o0 += tile) {
-                const uint32_t o1 = o0 + tile - 1 < outN ? o0 + tile - 1 : outN - 1;
-                best = std::max(best, t[o1].i0 + 2 - t[o0].i0);
-            }
-            return (uint32_t)best;
-        };
-        outsideCols_ = span(taps.data(), ow, 32);
-        outsideRows_[0] = span(taps.data() + bilYOff_, oh, 32);
-        outsideRows_[1] = span(taps.data() + bilYOff_, oh, 24);
-        hipError_t e = dev_malloc(reinterpret_cast<void **>(&bilinDev_), taps.size() * sizeof(BilinTap));
-        if (e == hipSuccess) e = hipMemcpy(bilinDev_, taps.data(), taps.size() * sizeof(BilinTap), hipMemcpyHostToDevice);
+    if (plan_.doUpscale) {
+        hipError_t e = dev_malloc(reinterpret_cast<void **>(&bilinDev_), plan_.taps.size() * sizeof(BilinTap));
+        if (e == hipSuccess) e = hipMemcpy(bilinDev_, plan_.taps.data(), plan_.taps.size() * sizeof(BilinTap), hipMemcpyHostToDevice);
         if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("bilinear tap tables: ") + hipGetErrorString(e));
     }
-    if (doUpscale_ && ProductArithmetic() && (maskMode_[0] == MASK_MIXED || maskMode_[1] == MASK_MIXED)) {
-        const bool nis = cfg_.use_nis != 0; // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
-        int rc = PrepareTileLists(nis ? 32 : kTileW, nis ? 24 : kTileH, nis ? 32 : 16, nis ? 24 : 16);
-        if (rc != OVRFSR_OK) return rc;
+    if (plan_.tileLists) {
+        const std::vector<uint32_t> &lists = plan_.lists, &recs = plan_.recs, &spans = plan_.spans;
+        const size_t listDwords = (lists.size() + 3) & ~(size_t)3; // the records follow the lists, 16-byte aligned
+        hipError_t e = dev_malloc(reinterpret_cast<void **>(&tileListDev_), (listDwords + recs.size() + spans.size()) * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(tileListDev_, lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            tileRecDev_ = tileListDev_ + listDwords;
+            e = hipMemcpy(tileRecDev_, recs.data(), recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        }
+        if (e == hipSuccess && !spans.empty()) {
+            spanRecDev_ = tileRecDev_ + recs.size();
+            e = hipMemcpy(spanRecDev_, spans.data(), spans.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("tile lists: ") + hipGetErrorString(e));
+        // the host copies have served (several MB at 16384^2); the per-call path reads the plan's counts and offsets only
+        for (std::vector<uint32_t> *v : {&plan_.lists, &plan_.recs, &plan_.spans}) std::vector<uint32_t>().swap(*v);
     }
-    if (doSharpen_ && !cfg_.use_nis) PrepareSharpeningResources();
-    // one launch with the intermediate in LDS only on request: on this chip both stages are VALU-bound and the ring
-    // recompute costs more than the HBM round trip saves, so auto (-1) means two kernels
-    useFused_ = false;
-    // auto: masked product-build pipelines run fused + mask-sorted (most of their pixels are plain bilinear copies, and tiles outside the
-    // radius need no intermediate at all); unmasked ones stay two-pass (VALU-bound, the ring recompute costs 9 %)
-    const bool tenBit = in.format == OVRFSR_FORMAT_RGB10A2_UNORM; // two-kernel pipeline only (header)
-    if (tenBit && cfg_.fused == 1) return Fail(OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for RGB10A2 images");
-    // cfg.reference_formats with a float pipeline input (R11G11B10F counts as RGBA16F here): the intermediate is UNORM8, and no fused kernel is
-    // built for a byte intermediate of a float source -- two-kernel forms only, the mask-sorted one where there is a mask
-    const bool floatIn = in.format == OVRFSR_FORMAT_RGBA16F || in.format == OVRFSR_FORMAT_RGBA32F;
-    if (cfg_.reference_formats && floatIn && cfg_.fused == 1)
-        return Fail(OVRFSR_ERR_UNSUPPORTED, "the fused kernel is not built for float images under reference_formats (UNORM8 intermediate of a float source)");
-    const bool byteMidOfFloat = floatIn && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
-    const bool autoFused = !tenBit && !byteMidOfFloat && cfg_.fused == -1 && tileListDev_ != nullptr && fusedCellsW_ <= 40 &&
-                           fused_lds_bytes(LaunchPrec(), (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) <= kFusedLdsMax;
-    // auto on a masked product-build EASU+RCAS pipeline: the two-pass kernels on the tiles touching the radius, tiles
-    // outside written in final form (ApplySorted); cfg.fused = 1 keeps the single fused kernel on those tiles
-    // Measured: with 4-byte pixels the sorted two-pass form wins (C2 shape, radius 0.5: +13 %); with 8/16-byte
-    // pixels the outside kernel dominates the frame, and the three dependent launches of the sorted form lose to the
-    // fused kernel (C5: -15 %), so those keep it.  The condition is the INTERMEDIATE's format: under cfg.reference_formats a float source
-    // has a UNORM8 intermediate too, and takes this form (RCAS on rcas_dpp_kernel's span records; profiles/reference_formats.txt).
-    useSorted_ = cfg_.fused == -1 && tileListDev_ != nullptr && doUpscale_ && doSharpen_ && !cfg_.use_nis &&
-                 (in.format == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) && IntermediateFormat() == OVRFSR_FORMAT_RGBA8_UNORM;
-    if ((cfg_.fused == 1 || (autoFused && !useSorted_)) && doUpscale_ && doSharpen_ && !cfg_.use_nis) {
-        const bool pitchOk = LaunchPrec() == PREC_FP32_STRICT || fusedCellsW_ <= 40;
-        if (!pitchOk || fused_lds_bytes(LaunchPrec(), (int)in.format, (int)IntermediateFormat(), fusedCellsW_, fusedCellsH_) > kFusedLdsMax)
-            return Fail(OVRFSR_ERR_UNSUPPORTED, "fused kernel: tile footprint does not fit LDS at this scale");
-        useFused_ = true;
-    }
-    if (useFused_ && cfg_.precision == OVRFSR_PRECISION_FP32_EXACT) // (fused = -1 picks it for half / float intermediates only, refused above)
-        return Fail(OVRFSR_ERR_UNSUPPORTED, "precision FP32_EXACT: the fused kernel has no exact-stores form");
     if (cfg_.debug_mode) {
         // every slot is checked on its own: a creation that failed half-way through the ring (found by fault injection, round 6: slot 0 existed,
         // a later one did not, and the rebuild after reset skipped the whole ring -- hipEventRecord on a null event) is completed by the next build
@@ -479,160 +279,9 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted)
     return OVRFSR_OK;
 }
 
-// Block b of a launch runs on XCD b % 8, each XCD with a private L2: entry b of a work list of n row-major items is item
-// xcd_source(b, n), which hands every XCD a contiguous raster run of the list (the n % 8 trailing entries keep their place).
-static inline uint32_t xcd_source(uint32_t b, uint32_t n)
-{
-    const uint32_t full = n & ~7u;
-    return b < full ? (b & 7u) * (full >> 3) + (b >> 3) : b;
-}
-
-// The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one 16x16 group
-// inside the radius (EASU kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel).
-int PostProcessor::PrepareTileLists(uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH)
-{
-    const uint32_t tx = (outputWidth_ + tileW - 1) / tileW, ty = (outputHeight_ + tileH - 1) / tileH;
-    const uint32_t gpx = tileW / groupW, gpy = tileH / groupH; // mask groups per tile
-    std::vector<uint32_t> lists;
-    std::vector<uint32_t> in[2], outl[2];
-    for (int eye = 0; eye < 2; ++eye) {
-        for (uint32_t t = 0; t < tx * ty; ++t) {
-            const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            bool any = false;
-            for (uint32_t g = 0; g < gpx * gpy && !any; ++g) {
-                const uint32_t gx = gpx * txi + (g % gpx), gy = gpy * tyi + (g / gpx);
-                const uint32_t cx = gx * groupW + groupW / 2, cy = gy * groupH + groupH / 2;
-                const uint32_t ax = centre_[eye][0] - cx, ay = centre_[eye][1] - cy, bx = centre_[eye][2] - cx, by = centre_[eye][3] - cy;
-                any = (ax * ax + ay * ay <= radius_[1]) || (bx * bx + by * by <= radius_[1]);
-            }
-            (any ? in[eye] : outl[eye]).push_back(t);
-        }
-    }
-    std::vector<uint32_t> ring[2];
-    for (int eye = 0; eye < 2; ++eye) {
-        std::vector<uint8_t> isIn(tx * ty, 0);
-        for (uint32_t t : in[eye]) isIn[t] = 1;
-        for (uint32_t t : outl[eye]) {
-            const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            const bool adj = (txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx]);
-            if (adj) ring[eye].push_back(t);
-        }
-    }
-    listsShared_ = in[0] == in[1];
-    // RCAS on the mask-sorted form (RGBA8): per 32-row band, runs of adjacent tiles touching the radius, cut into the DPP
-    // kernel's 62-column segments (rcas_dpp_kernel<.., true>): {x0 | tileY << 16, xEnd}
-    std::vector<uint32_t> spans;
-    nSpans_[0] = nSpans_[1] = 0;
-    if (tileW == kTileW && tileH == kRcasDppTileH && outputWidth_ < 65536u && ty < 65536u) {
-        for (int eye = 0; eye < 2; ++eye) {
-            spanOff_[eye] = spans.size() / 2;
-            for (size_t i = 0; i < in[eye].size();) { // in[] is row-major here
-                size_t j = i;
-                while (j + 1 < in[eye].size() && in[eye][j + 1] == in[eye][j] + 1 && (in[eye][j + 1] / tx) == (in[eye][i] / tx)) ++j;
-                const uint32_t tyi = in[eye][i] / tx, xa = (in[eye][i] - tyi * tx) * tileW;
-                const uint32_t xb = std::min((in[eye][j] - tyi * tx + 1) * tileW, outputWidth_);
-                for (uint32_t x0 = xa; x0 < xb; x0 += kRcasDppTileW) {
-                    spans.push_back(x0 | (tyi << 16));
-                    spans.push_back(std::min(x0 + (uint32_t)kRcasDppTileW, xb));
-                }
-                i = j + 1;
-            }
-            nSpans_[eye] = (uint32_t)(spans.size() / 2 - spanOff_[eye]);
-            // every XCD a contiguous raster run of segments (xcd_source), so that the 128-byte lines two neighbouring
-            // segments share, and the rows two bands share, are fetched once
-            const uint32_t n = nSpans_[eye];
-            std::vector<uint32_t> r(2 * (size_t)n);
-            for (uint32_t b = 0; b < n; ++b) {
-                const size_t src = spanOff_[eye] + xcd_source(b, n);
-                r[2 * (size_t)b] = spans[2 * src]; r[2 * (size_t)b + 1] = spans[2 * src + 1];
-            }
-            std::copy(r.begin(), r.end(), spans.begin() + 2 * spanOff_[eye]);
-        }
-    }
-    auto xcd_order = [](std::vector<uint32_t> &v) {
-        const uint32_t n = (uint32_t)v.size();
-        std::vector<uint32_t> r(n);
-        for (uint32_t b = 0; b < n; ++b) r[b] = v[xcd_source(b, n)];
-        v.swap(r);
-    };
-    for (int eye = 0; eye < 2; ++eye) {
-        xcd_order(in[eye]); xcd_order(outl[eye]);
-        nInside_[eye] = (uint32_t)in[eye].size(); nOutside_[eye] = (uint32_t)outl[eye].size();
-        // inside | ring | outside: the ring tiles follow the inside tiles so that ONE EASU launch over nInside + nRing entries
-        // also writes the bilinear intermediate of the ring (its all-outside path), while RCAS walks the first nInside only
-        listOffInside_[eye] = lists.size(); lists.insert(lists.end(), in[eye].begin(), in[eye].end());
-        nRing_[eye] = (uint32_t)ring[eye].size();
-        listOffRing_[eye] = lists.size(); lists.insert(lists.end(), ring[eye].begin(), ring[eye].end());
-        listOffOutside_[eye] = lists.size(); lists.insert(lists.end(), outl[eye].begin(), outl[eye].end());
-    }
-    if (lists.empty()) return OVRFSR_OK;
-    // One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin
-    // (first column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of
-    // dependent scalar loads: tile index -> tap tables)
-    std::vector<uint32_t> recs(lists.size() * 4, 0u);
-    if (bilinHost_.size() >= (size_t)bilYOff_ + outputHeight_) {
-        const BilinTap *bx = bilinHost_.data(), *by = bilinHost_.data() + bilYOff_;
-        const uint32_t rowsCap = outsideRows_[tileH == 24 ? 1 : 0];
-        for (size_t i = 0; i < lists.size(); ++i) {
-            const uint32_t t = lists[i], tyi = t / tx, txi = t - tyi * tx;
-            const uint32_t ox0 = txi * tileW, oy0 = tyi * tileH;
-            const int X0 = bx[ox0].i0, Y0 = by[oy0].i0;
-            const int colsN = std::min<int>((int)outsideCols_, bx[std::min(ox0 + tileW - 1, outputWidth_ - 1)].i0 + 2 - X0);
-            const int rowsN = std::min<int>((int)rowsCap, by[std::min(oy0 + tileH - 1, outputHeight_ - 1)].i0 + 2 - Y0);
-            recs[4 * i + 0] = ox0 | (oy0 << 16);
-            recs[4 * i + 1] = (uint32_t)(X0 + 1) | ((uint32_t)(Y0 + 1) << 16);
-            recs[4 * i + 2] = (uint32_t)colsN | ((uint32_t)rowsN << 8);
-        }
-    }
-    const size_t listDwords = (lists.size() + 3) & ~(size_t)3; // the records follow the lists, 16-byte aligned
-    hipError_t e = dev_malloc(reinterpret_cast<void **>(&tileListDev_), (listDwords + recs.size() + spans.size()) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(tileListDev_, lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        tileRecDev_ = tileListDev_ + listDwords;
-        e = hipMemcpy(tileRecDev_, recs.data(), recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && !spans.empty()) {
-        spanRecDev_ = tileRecDev_ + recs.size();
-        e = hipMemcpy(spanRecDev_, spans.data(), spans.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("tile lists: ") + hipGetErrorString(e));
-    return OVRFSR_OK;
-}
-
-int PostProcessor::PrepareNisResources()
-{
-    std::memset(&nisConfig_, 0, sizeof(nisConfig_));
-    // NVScalerUpdateConfig (scale != 1) or NVSharpenUpdateConfig (out == in), PostProcessor.cpp:308,:433.
-    // The reference ignores a `false` result and dispatches with a half-filled block; that is undefined
-    // there, so it is an error here.
-    if (!nis_scaler_config(&nisConfig_, cfg_.sharpness, inputWidth_, inputHeight_, outputWidth_, outputHeight_))
-        return Fail(OVRFSR_ERR_UNSUPPORTED, "NIS scales 1x..2x only (NVScalerUpdateConfig returned false)");
-    nisConfig_.reserved1 = cfg_.debug_mode ? 1.f : 0.f; // :309
-    if (doUpscale_) {
-        auto extent = [](uint32_t outN, int blk, float s) {
-            int best = 0;
-            for (uint32_t o0 = 0; o0 < outN; o0 += blk) {
-                uint32_t o1 = o0 + blk - 1 < outN ? o0 + blk - 1 : outN - 1;
-                int f0 = (int)std::floor(mad2(0.5f + (float)o0, s, -0.5f)), f1 = (int)std::floor(mad2(0.5f + (float)o1, s, -0.5f));
-                best = f1 - f0 + 7 > best ? f1 - f0 + 7 : best; // 6-tap support (+2/+3) and the edge-map ring (+1)
-            }
-            return best;
-        };
-        nisCellsW_ = extent(outputWidth_, 32, nisConfig_.kScaleX);
-        nisCellsH_ = extent(outputHeight_, 24, nisConfig_.kScaleY);
-        if (nis_pitch(nisCellsW_) == 0 || nis_scaler_lds_bytes(nisCellsW_, nisCellsH_) > 64 * 1024)
-            return Fail(OVRFSR_ERR_UNSUPPORTED, "NIS tile does not fit LDS");
-    }
-    hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(nisCoefDev_, nis_coef_scale(), 512 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(nisCoefDev_ + 512, nis_coef_usm(), 512 * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("NIS coefficient upload: ") + hipGetErrorString(e));
-    return OVRFSR_OK;
-}
-
 void PostProcessor::FillNis(NisArgs &a, int firstEye, int alternate) const
 {
-    const NisConstants &c = nisConfig_;
+    const NisConstants &c = plan_.nis;
     a.kDetectRatio = c.kDetectRatio; a.kDetectThres = c.kDetectThres; a.kMinContrastRatio = c.kMinContrastRatio; a.kRatioNorm = c.kRatioNorm;
     a.kContrastBoost = c.kContrastBoost; a.kEps = c.kEps; a.kSharpStartY = c.kSharpStartY; a.kSharpScaleY = c.kSharpScaleY;
     a.kSharpStrengthMin = c.kSharpStrengthMin; a.kSharpStrengthScale = c.kSharpStrengthScale;
@@ -644,17 +293,17 @@ void PostProcessor::FillNis(NisArgs &a, int firstEye, int alternate) const
     a.tileRec = nullptr;
     a.coefScale = nisCoefDev_;
     a.coefUsm = nisCoefDev_ + 512;
-    a.cellsW = nisCellsW_; a.cellsH = nisCellsH_;
-    a.bilX = bilinDev_; a.bilY = bilinDev_ ? bilinDev_ + bilYOff_ : nullptr;
-    a.outsideCols = outsideCols_; a.outsideRows = outsideRows_[1];
+    a.cellsW = plan_.nisCellsW; a.cellsH = plan_.nisCellsH;
+    a.bilX = bilinDev_; a.bilY = bilinDev_ ? bilinDev_ + plan_.tapYOff : nullptr;
+    a.outsideCols = plan_.outsideCols; a.outsideRows = plan_.outsideRows[1];
 }
 
 void PostProcessor::FillMask(MaskArgs &m, int firstEye, int alternate) const
 {
-    std::memcpy(m.centre, centre_, sizeof(centre_));
-    m.r2 = radius_[1];
-    m.mode[0] = maskMode_[0];
-    m.mode[1] = maskMode_[1];
+    std::memcpy(m.centre, plan_.centre, sizeof(plan_.centre));
+    m.r2 = plan_.radius[1];
+    m.mode[0] = plan_.maskMode[0];
+    m.mode[1] = plan_.maskMode[1];
     m.first_eye = (uint32_t)(firstEye & 1);
     m.alternate = alternate ? 1u : 0u;
 }
@@ -683,7 +332,7 @@ int PostProcessor::Launched(hipError_t e, const char *what)
 // otherwise the images of each eye form their own stride-2 sub-batch (images p, p+2, ... have the same eye).
 int PostProcessor::EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const
 {
-    const bool twoEyes = alternate && n > 1 && !listsShared_;
+    const bool twoEyes = alternate && n > 1 && !plan_.listsShared;
     if (!twoEyes) {
         out[0] = EyePass{firstEye & 1, n, 0, 1, false};
         return 1;
@@ -704,11 +353,11 @@ void PostProcessor::EyePass::Select(Args &a) const
 // The masked ("mask-sorted") launch, whatever the kernels: the passes of EyePasses between Fork and Join, stopping at the first launch
 // that fails.  `body` launches one pass: the inside-list kernel on the caller's stream, then the outside-tile kernel on `aux`.
 template <class Body>
-int PostProcessor::ForEachEyePass(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, hipStream_t stream, const char *what, Body body)
+int PostProcessor::ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, const char *what, Body body)
 {
     EyePass passes[2];
     const int np = EyePasses(n, firstEye, alternate, passes);
-    hipStream_t aux = Fork(stream, OverlapOutside(in));
+    hipStream_t aux = Fork(stream, plan_.overlapOutside);
     hipError_t e = hipSuccess;
     for (int p = 0; p < np && e == hipSuccess; ++p) e = body(passes[p], aux);
     Join(stream, aux);
@@ -718,45 +367,45 @@ int PostProcessor::ForEachEyePass(uint32_t n, int firstEye, int alternate, const
 int PostProcessor::ApplyUpscaling(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
                                   const ovrfsr_image &out, size_t outStride, hipStream_t stream)
 {
-    if (cfg_.use_nis) {
+    if (plan_.useNis) {
         NisArgs na;
         na.v = make_view(in, inStride, out, outStride);
         FillNis(na, firstEye, alternate);
         na.tilesX = (out.width + 31) / 32;   // Dispatch(ceil(outW/32), ceil(outH/24)), :397
         na.tilesY = (out.height + 23) / 24;
         na.tileList = nullptr;
-        if (!tileListDev_) return Launched(launch_nis_scaler(LaunchPrec(), (int)in.format, (int)out.format, na, n, stream), "NVScaler");
-        return ForEachEyePass(n, firstEye, alternate, in, stream, "NVScaler", [&](const EyePass &ps, hipStream_t aux) {
+        if (!plan_.tileLists) return Launched(launch_nis_scaler(plan_.launchPrec, (int)in.format, (int)out.format, na, n, stream), "NVScaler");
+        return ForEachEyePass(n, firstEye, alternate, stream, "NVScaler", [&](const EyePass &ps, hipStream_t aux) {
             NisArgs b = na;
             ps.Select(b);
             hipError_t e = hipSuccess;
-            if (nInside_[ps.eye]) {
-                b.tileList = tileListDev_ + listOffInside_[ps.eye];
-                e = launch_nis_scaler(LaunchPrec(), (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
+            if (plan_.nInside[ps.eye]) {
+                b.tileList = tileListDev_ + plan_.listOffInside[ps.eye];
+                e = launch_nis_scaler(plan_.launchPrec, (int)in.format, (int)out.format, b, ps.cnt, stream, plan_.nInside[ps.eye]);
             }
-            if (e == hipSuccess && nOutside_[ps.eye]) {
-                b.tileList = tileListDev_ + listOffOutside_[ps.eye];
-                b.tileRec = tileRecDev_ + 4 * listOffOutside_[ps.eye];
-                e = launch_nis_outside((int)in.format, (int)out.format, b, nOutside_[ps.eye], ps.cnt, aux);
+            if (e == hipSuccess && plan_.nOutside[ps.eye]) {
+                b.tileList = tileListDev_ + plan_.listOffOutside[ps.eye];
+                b.tileRec = tileRecDev_ + 4 * plan_.listOffOutside[ps.eye];
+                e = launch_nis_outside((int)in.format, (int)out.format, b, plan_.nOutside[ps.eye], ps.cnt, aux);
             }
             return e;
         });
     }
     EasuArgs a;
     FillEasu(a, in, inStride, out, outStride, firstEye, alternate);
-    if (!tileListDev_) return Launched(launch_easu(LaunchPrec(), (int)in.format, (int)out.format, a, n, stream), "EASU");
-    return ForEachEyePass(n, firstEye, alternate, in, stream, "EASU", [&](const EyePass &ps, hipStream_t aux) {
+    if (!plan_.tileLists) return Launched(launch_easu(plan_.launchPrec, (int)in.format, (int)out.format, a, n, stream), "EASU");
+    return ForEachEyePass(n, firstEye, alternate, stream, "EASU", [&](const EyePass &ps, hipStream_t aux) {
         EasuArgs b = a;
         ps.Select(b);
         hipError_t e = hipSuccess;
-        if (nInside_[ps.eye]) {
-            b.tileList = tileListDev_ + listOffInside_[ps.eye];
-            e = launch_easu(LaunchPrec(), (int)in.format, (int)out.format, b, ps.cnt, stream, nInside_[ps.eye]);
+        if (plan_.nInside[ps.eye]) {
+            b.tileList = tileListDev_ + plan_.listOffInside[ps.eye];
+            e = launch_easu(plan_.launchPrec, (int)in.format, (int)out.format, b, ps.cnt, stream, plan_.nInside[ps.eye]);
         }
-        if (e == hipSuccess && nOutside_[ps.eye]) {
-            b.tileList = tileListDev_ + listOffOutside_[ps.eye];
-            b.tileRec = tileRecDev_ + 4 * listOffOutside_[ps.eye];
-            e = launch_easu_outside((int)in.format, -1, (int)out.format, b, nOutside_[ps.eye], ps.cnt, aux);
+        if (e == hipSuccess && plan_.nOutside[ps.eye]) {
+            b.tileList = tileListDev_ + plan_.listOffOutside[ps.eye];
+            b.tileRec = tileRecDev_ + 4 * plan_.listOffOutside[ps.eye];
+            e = launch_easu_outside((int)in.format, -1, (int)out.format, b, plan_.nOutside[ps.eye], ps.cnt, aux);
         }
         return e;
     });
@@ -768,13 +417,13 @@ void PostProcessor::FillScale(Args &a, const ovrfsr_image &in, size_t inStride, 
                               int firstEye, int alternate) const
 {
     a.v = make_view(in, inStride, out, outStride);
-    std::memcpy(&a.sx, &easuCon_[0], 4); std::memcpy(&a.sy, &easuCon_[1], 4);
-    std::memcpy(&a.cx, &easuCon_[2], 4); std::memcpy(&a.cy, &easuCon_[3], 4);
+    std::memcpy(&a.sx, &plan_.easuCon[0], 4); std::memcpy(&a.sy, &plan_.easuCon[1], 4);
+    std::memcpy(&a.cx, &plan_.easuCon[2], 4); std::memcpy(&a.cy, &plan_.easuCon[3], 4);
     FillMask(a.m, firstEye, alternate);
-    a.bilX = bilinDev_; a.bilY = bilinDev_ + bilYOff_;
+    a.bilX = bilinDev_; a.bilY = bilinDev_ + plan_.tapYOff;
     a.tileList = nullptr;
     a.tieHalfMin = TieHalfMin();
-    a.debug = rcasCon_[3];
+    a.debug = plan_.rcasCon[3];
     a.tilesX = (out.width + kTileW - 1) / kTileW;   // the reference dispatches 16x16 groups (PostProcessor.cpp:399);
     a.tilesY = (out.height + kTileH - 1) / kTileH;  // a tile here is 2x2 of those
 }
@@ -783,11 +432,11 @@ void PostProcessor::FillEasu(EasuArgs &a, const ovrfsr_image &in, size_t inStrid
                              int firstEye, int alternate) const
 {
     FillScale(a, in, inStride, out, outStride, firstEye, alternate);
-    a.cellsW = cellsW_; a.cellsH = cellsH_;
+    a.cellsW = plan_.cellsW; a.cellsH = plan_.cellsH;
     a.tileRec = nullptr;
     a.ringStrips = 0;
-    a.rcpOutW = rcpOut_[0]; a.rcpOutH = rcpOut_[1]; a.rcpExact = rcpExact_ ? 1u : 0u;
-    a.outsideCols = outsideCols_; a.outsideRows = outsideRows_[0];
+    a.rcpOutW = plan_.rcpOut[0]; a.rcpOutH = plan_.rcpOut[1]; a.rcpExact = plan_.rcpExact ? 1u : 0u;
+    a.outsideCols = plan_.outsideCols; a.outsideRows = plan_.outsideRows[0];
     // UNORM8 store of a float source (easu_fast_kernel<RGBA16F / RGBA32F, RGBA8>: the kernel has no half store, so the field is its guard's
     // SWITCH): +inf = off, the stores of every earlier release; finite = on, the store is the strict build's bit for bit.  On exactly
     // under cfg.reference_formats -- the pipeline's UNORM8 intermediate and an EASU-only RGBA8 output alike.
@@ -799,8 +448,8 @@ void PostProcessor::FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStrid
                              int firstEye, int alternate) const
 {
     a.v = make_view(in, inStride, out, outStride);
-    std::memcpy(&a.sharp, &rcasCon_[0], 4);
-    a.debug = rcasCon_[3];
+    std::memcpy(&a.sharp, &plan_.rcasCon[0], 4);
+    a.debug = plan_.rcasCon[3];
     FillMask(a.m, firstEye, alternate);
     a.tilesX = (out.width + kTileW - 1) / kTileW;
     a.tilesY = (out.height + kTileH - 1) / kTileH;
@@ -808,10 +457,8 @@ void PostProcessor::FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStrid
     a.spanRec = nullptr; a.nSpans = 0;
 }
 
-// Near-tie guard of a half-float intermediate: the smallest value whose flipped half rounding could exceed the 1e-3 tolerance
-// behind RCAS.  RCAS's gain on its centre tap is at most 1 / (1 - 4 * 0.1875 * sharp) (lobe >= -FSR_RCAS_LIMIT * sharp,
-// ffx_fsr1.h:654,757-765); a half in [b, 2b) moves in steps of b * 2^-10.  Binades whose step times that gain stays under
-// 9e-4 are left alone; +inf (guard off) when no sharpening pass follows the upscale.
+// Near-tie guard of a half-float intermediate (plan_pipeline): the smallest value whose flipped half rounding could exceed the 1e-3 tolerance
+// behind RCAS; +inf (guard off) when no sharpening pass follows the upscale.
 float PostProcessor::TieHalfMin() const
 {
 #ifdef OVRFSR_TIE_AUDIT
@@ -821,13 +468,7 @@ float PostProcessor::TieHalfMin() const
     static const float forced = [] { const char *e = std::getenv("OVRFSR_TIE_HALF_MIN"); return e ? (float)std::atof(e) : 0.0f; }();
     if (forced > 0.0f) return forced;
 #endif
-    if (!(doUpscale_ && doSharpen_) || cfg_.use_nis) return INFINITY;
-    float sharp;
-    std::memcpy(&sharp, &rcasCon_[0], 4);
-    const float gain = 1.0f / (1.0f - 0.75f * sharp);
-    float b = 1.0f / 16384.0f; // half's smallest normal binade
-    while (b < 65536.0f && gain * b * (1.0f / 1024.0f) < 9e-4f) b *= 2.0f;
-    return b;
+    return plan_.tieHalfMin;
 }
 
 // Masked EASU+RCAS, product build.  Main stream: EASU on the tiles touching the radius -> intermediate; the bilinear
@@ -846,7 +487,7 @@ int PostProcessor::ApplySorted(uint32_t n, int firstEye, int alternate, const ov
     FillEasu(toOut, in, inStride, out, outStride, firstEye, alternate);
     RcasArgs ra;
     FillRcas(ra, mid, midStride, out, outStride, firstEye, alternate);
-    return ForEachEyePass(n, firstEye, alternate, in, stream, "mask-sorted EASU+RCAS", [&](const EyePass &ps, hipStream_t aux) {
+    return ForEachEyePass(n, firstEye, alternate, stream, "mask-sorted EASU+RCAS", [&](const EyePass &ps, hipStream_t aux) {
         EasuArgs em = toMid, eo = toOut;
         RcasArgs rb = ra;
         ps.Select(em); ps.Select(eo); ps.Select(rb);
@@ -856,20 +497,20 @@ int PostProcessor::ApplySorted(uint32_t n, int firstEye, int alternate, const ov
         // covers the inside tiles AND the ring (outside tiles 4-adjacent to them, listed right behind: RCAS taps reach one
         // pixel across a tile edge); its all-outside path writes their bilinear intermediate, the same bytes the separate
         // ring launch of rounds 1-2 wrote
-        if (nInside_[eye]) {
-            em.tileList = tileListDev_ + listOffInside_[eye];
+        if (plan_.nInside[eye]) {
+            em.tileList = tileListDev_ + plan_.listOffInside[eye];
             em.ringStrips = 1; // of a ring tile, RCAS only reads the pixels next to an inside tile
-            e = launch_easu(LaunchPrec(), (int)in.format, (int)mid.format, em, ps.cnt, stream, nInside_[eye] + nRing_[eye]);
+            e = launch_easu(plan_.launchPrec, (int)in.format, (int)mid.format, em, ps.cnt, stream, plan_.nInside[eye] + plan_.nRing[eye]);
         }
-        if (e == hipSuccess && nOutside_[eye]) {
-            eo.tileList = tileListDev_ + listOffOutside_[eye];
-            eo.tileRec = tileRecDev_ + 4 * listOffOutside_[eye];
-            e = launch_easu_outside((int)in.format, (int)mid.format, (int)out.format, eo, nOutside_[eye], ps.cnt, aux);
+        if (e == hipSuccess && plan_.nOutside[eye]) {
+            eo.tileList = tileListDev_ + plan_.listOffOutside[eye];
+            eo.tileRec = tileRecDev_ + 4 * plan_.listOffOutside[eye];
+            e = launch_easu_outside((int)in.format, (int)mid.format, (int)out.format, eo, plan_.nOutside[eye], ps.cnt, aux);
         }
-        if (e == hipSuccess && nInside_[eye]) {
-            rb.tileList = tileListDev_ + listOffInside_[eye];
-            if (spanRecDev_ && nSpans_[eye]) { rb.spanRec = spanRecDev_ + 2 * spanOff_[eye]; rb.nSpans = nSpans_[eye]; }
-            e = launch_rcas(cfg_.precision, (int)mid.format, (int)out.format, rb, ps.cnt, stream, nInside_[eye]);
+        if (e == hipSuccess && plan_.nInside[eye]) {
+            rb.tileList = tileListDev_ + plan_.listOffInside[eye];
+            if (spanRecDev_ && plan_.nSpans[eye]) { rb.spanRec = spanRecDev_ + 2 * plan_.spanOff[eye]; rb.nSpans = plan_.nSpans[eye]; }
+            e = launch_rcas(plan_.rcasPrec, (int)mid.format, (int)out.format, rb, ps.cnt, stream, plan_.nInside[eye]);
         }
         return e;
     });
@@ -880,27 +521,27 @@ int PostProcessor::ApplyFused(uint32_t n, int firstEye, int alternate, const ovr
 {
     FusedArgs a;
     FillScale(a, in, inStride, out, outStride, firstEye, alternate);
-    std::memcpy(&a.sharp, &rcasCon_[0], 4);
-    a.cellsW = fusedCellsW_; a.cellsH = fusedCellsH_;
-    const int midFormat = (int)IntermediateFormat();
-    if (!tileListDev_) return Launched(launch_fused(LaunchPrec(), (int)in.format, midFormat, (int)out.format, a, n, stream), "fused EASU+RCAS");
+    std::memcpy(&a.sharp, &plan_.rcasCon[0], 4);
+    a.cellsW = plan_.fusedCellsW; a.cellsH = plan_.fusedCellsH;
+    const int midFormat = (int)plan_.intermediateFormat;
+    if (!plan_.tileLists) return Launched(launch_fused(plan_.launchPrec, (int)in.format, midFormat, (int)out.format, a, n, stream), "fused EASU+RCAS");
     // masked: tiles entirely outside the radius never need an intermediate (RCAS there is a tinted copy), they are
     // written in final form by the LDS-free bilinear kernel; only tiles touching the radius run the fused kernel
     EasuArgs ea;
     FillEasu(ea, in, inStride, out, outStride, firstEye, alternate);
-    return ForEachEyePass(n, firstEye, alternate, in, stream, "fused EASU+RCAS", [&](const EyePass &ps, hipStream_t aux) {
+    return ForEachEyePass(n, firstEye, alternate, stream, "fused EASU+RCAS", [&](const EyePass &ps, hipStream_t aux) {
         FusedArgs fb = a;
         EasuArgs eb = ea;
         ps.Select(fb); ps.Select(eb);
         hipError_t e = hipSuccess;
-        if (nInside_[ps.eye]) {
-            fb.tileList = tileListDev_ + listOffInside_[ps.eye];
-            e = launch_fused(LaunchPrec(), (int)in.format, midFormat, (int)out.format, fb, ps.cnt, stream, nInside_[ps.eye]);
+        if (plan_.nInside[ps.eye]) {
+            fb.tileList = tileListDev_ + plan_.listOffInside[ps.eye];
+            e = launch_fused(plan_.launchPrec, (int)in.format, midFormat, (int)out.format, fb, ps.cnt, stream, plan_.nInside[ps.eye]);
         }
-        if (e == hipSuccess && nOutside_[ps.eye]) {
-            eb.tileList = tileListDev_ + listOffOutside_[ps.eye];
-            eb.tileRec = tileRecDev_ + 4 * listOffOutside_[ps.eye];
-            e = launch_easu_outside((int)in.format, midFormat, (int)out.format, eb, nOutside_[ps.eye], ps.cnt, aux);
+        if (e == hipSuccess && plan_.nOutside[ps.eye]) {
+            eb.tileList = tileListDev_ + plan_.listOffOutside[ps.eye];
+            eb.tileRec = tileRecDev_ + 4 * plan_.listOffOutside[ps.eye];
+            e = launch_easu_outside((int)in.format, midFormat, (int)out.format, eb, plan_.nOutside[ps.eye], ps.cnt, aux);
         }
         return e;
     });
@@ -909,52 +550,29 @@ int PostProcessor::ApplyFused(uint32_t n, int firstEye, int alternate, const ovr
 int PostProcessor::ApplySharpening(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
                                    const ovrfsr_image &out, size_t outStride, hipStream_t stream)
 {
-    if (cfg_.use_nis) {
+    if (plan_.useNis) {
         NisArgs na;
         na.v = make_view(in, inStride, out, outStride);
         FillNis(na, firstEye, alternate);
         na.tilesX = (out.width + 31) / 32;   // Dispatch(ceil(outW/32), ceil(outH/32)), :492
         na.tilesY = (out.height + 31) / 32;
         na.tileList = nullptr;
-        return Launched(launch_nis_sharpen(LaunchPrec(), (int)in.format, (int)out.format, na, n, stream), "NVSharpen");
+        return Launched(launch_nis_sharpen(plan_.launchPrec, (int)in.format, (int)out.format, na, n, stream), "NVSharpen");
     }
     RcasArgs a;
     FillRcas(a, in, inStride, out, outStride, firstEye, alternate);
-    return Launched(launch_rcas(cfg_.precision, (int)in.format, (int)out.format, a, n, stream), "RCAS");
+    return Launched(launch_rcas(plan_.rcasPrec, (int)in.format, (int)out.format, a, n, stream), "RCAS");
 }
 
 // `in`/`out` describe image 0 of a batch of n; `out` is the FINAL destination.
-// 4-sample RGBA8 on C2's path -- product build, unmasked easu_fast_kernel, two-kernel pipeline with a UNORM8 intermediate or EASU-only into
-// UNORM8 -- is resolved inside EASU's staging sweep (FMT_RGBA8_MS4, the same resolve_unorm8 the resolve pass runs: identical staged bytes,
-// identical output); every other multisampled input takes the resolve pass.  -DOVRFSR_MSAA_RESOLVE_PASS (measurement build, never shipped)
-// sends this path through the resolve pass too: the A/B of profiles/msaa_c2.txt.
-bool PostProcessor::ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const
-{
-#ifdef OVRFSR_MSAA_RESOLVE_PASS
-    (void)in; (void)out;
-    return false;
-#else
-    const bool unmasked = !tileListDev_ && maskMode_[0] == MASK_ALL_INSIDE && maskMode_[1] == MASK_ALL_INSIDE;
-    const uint32_t easuOut = doSharpen_ ? IntermediateFormat() : out.format;
-    return in.format == (uint32_t)FMT_RGBA8_MS4 && doUpscale_ && !cfg_.use_nis && !useSorted_ && !useFused_ && unmasked &&
-           easu_msaa_fused_ok(LaunchPrec(), (int)easuOut, cellsW_);
-#endif
-}
-
 int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &submitted, size_t submittedStride,
                                     const ovrfsr_image &out, size_t outStride, hipStream_t stream)
 {
     // Refusals first: nothing is built or launched for a call that is refused.  (Every destination has been through CheckImage, which
     // refuses R11G11B10F and multisampled ones of any base format: of the input-only formats only single-sample BGRA8 gets this far.)
-    if (const char *why = input_only(out.format)) return Fail(OVRFSR_ERR_UNSUPPORTED, why);
-    // R10G10B10A2 exists for the reference's 10-bit path: 10-bit in -> 10-bit out (or float, to measure parity)
-    const bool inTen = pipeline_format(submitted.format) == OVRFSR_FORMAT_RGB10A2_UNORM, outTen = out.format == OVRFSR_FORMAT_RGB10A2_UNORM;
-    if ((outTen && !inTen) || (inTen && !outTen && out.format != OVRFSR_FORMAT_RGBA32F))
-        return Fail(OVRFSR_ERR_UNSUPPORTED, "RGB10A2 images pair with an RGB10A2 (or RGBA32F) destination only");
-    // (a float intermediate in front of a 10-bit destination is a kernel pair nobody builds: refused here, before anything is launched,
-    // instead of surfacing as a launch error behind the EASU pass -- found by the round-6 format sweep)
-    if (outTen && doUpscale_ && doSharpen_ && IntermediateFormat() != OVRFSR_FORMAT_RGB10A2_UNORM)
-        return Fail(OVRFSR_ERR_UNSUPPORTED, "RGB10A2 pipelines keep a 10-bit intermediate (quantize_intermediate = 1)");
+    // (Apply / ApplyBatch have asked the same question through RefuseDisablingDestination and acted on the refusals that disable the ctx;
+    // what is left for this evaluation are the others, also for a pair_submit eye that was recorded and is launched by FlushPending.)
+    if (const Refusal refused = destination_refusal(plan_, out.format)) return Fail(refused.status, refused.text);
 
     // The pipeline's input: the submission itself, or a ctx-owned copy of it in pipeline_format.
     // (the ring is complete: slots are created in order; a call that is being captured into a graph is not timed: its events could never be read back)
@@ -962,7 +580,7 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
     ovrfsr_image in = submitted;
     size_t inStride = submittedStride;
     const uint32_t base = base_format(submitted.format), samples = format_samples(submitted.format);
-    if ((samples > 1u || base == OVRFSR_FORMAT_R11G11B10F) && !ResolveInStaging(submitted, out)) {
+    if ((samples > 1u || base == OVRFSR_FORMAT_R11G11B10F) && !resolve_in_staging(plan_, out.format)) {
         // the reference resolves a multisampled submission into a single-sample copy of its own format (PostProcessor.cpp:196-224,520-523):
         // one resolve pass (BGRA8 re-ordered in it), then the single-sample pipeline on the copy.  An R11G11B10F submission of any sample
         // count, 1 included, takes the same pass: it unpacks the words to an RGBA16F copy (the sampler's decode in the reference: header),
@@ -996,21 +614,31 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
     }
 
     int rc = OVRFSR_OK;
-    if (useSorted_) {
+    switch (plan_.form) {
+    case Form::MaskSorted:
         rc = ApplySorted(n, firstEye, alternate, in, inStride, out, outStride, stream);
-    } else if (useFused_) {
+        break;
+    case Form::Fused:
+    case Form::FusedMaskedOutside:
         rc = ApplyFused(n, firstEye, alternate, in, inStride, out, outStride, stream);
-    } else if (doUpscale_ && doSharpen_) {
+        break;
+    case Form::TwoPass: {
         ovrfsr_image mid;
         size_t midStride;
         rc = IntermediateImage(n, &mid, &midStride);
         if (rc != OVRFSR_OK) return rc;
         rc = ApplyUpscaling(n, firstEye, alternate, in, inStride, mid, midStride, stream);
         if (rc == OVRFSR_OK) rc = ApplySharpening(n, firstEye, alternate, mid, midStride, out, outStride, stream);
-    } else if (doUpscale_) {
+        break;
+    }
+    case Form::UpscaleOnly:
         rc = ApplyUpscaling(n, firstEye, alternate, in, inStride, out, outStride, stream);
-    } else if (doSharpen_) {
+        break;
+    case Form::SharpenOnly:
         rc = ApplySharpening(n, firstEye, alternate, in, inStride, out, outStride, stream);
+        break;
+    case Form::None:
+        break;
     }
     if (timing) {
         (void)hipEventRecord(queries_[currentQuery_].end, stream);
@@ -1051,9 +679,9 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
     if (guard.err != hipSuccess) return Fail(OVRFSR_ERR_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
 
     capturing_ = stream_capturing(stream);
-    if (capturing_ && (!initialized_ || in->width != inputWidth_ || in->height != inputHeight_ || in->format != inputFormat_))
+    if (capturing_ && (!initialized_ || in->width != plan_.inputWidth || in->height != plan_.inputHeight || in->format != plan_.inputFormat))
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, kCaptureRefusal); // (nothing touched: the capture stays valid, the ctx stays enabled)
-    if (initialized_ && (in->width != inputWidth_ || in->height != inputHeight_ || in->format != inputFormat_)) {
+    if (initialized_ && (in->width != plan_.inputWidth || in->height != plan_.inputHeight || in->format != plan_.inputFormat)) {
         bool keep = false;
         if (havePending_) { // the recorded eye belongs to the old resources
             const uint8_t *po = static_cast<const uint8_t *>(pendingOut_.data), *sb = static_cast<const uint8_t *>(sharpened_.p);
@@ -1069,25 +697,24 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         ResetKeeping(keep); // "Texture size changed, recreating resources" (:139-142)
     }
     if (!initialized_) {
-        textureContainsOnlyOneEye_ = std::fabs(bounds->uMax - bounds->uMin) > .5f; // :146
-        rc = PrepareResources(*in);
+        rc = PrepareResources(*in, std::fabs(bounds->uMax - bounds->uMin) > .5f); // :146
         if (rc != OVRFSR_OK) { enabled_ = false; return rc; } // :148-151
     }
 
     // caller-owned or ctx-owned final image
     ovrfsr_image dst;
-    const bool stages = doUpscale_ || doSharpen_;
+    const bool stages = plan_.doUpscale || plan_.doSharpen;
     // cfg.pair_submit (header): one texture per eye and something to launch -> the first eye of a frame is recorded, the other eye launches both
-    const bool pairMode = cfg_.pair_submit != 0 && textureContainsOnlyOneEye_ && stages;
+    const bool pairMode = cfg_.pair_submit != 0 && plan_.onlyOneEye && stages;
     if (out->data) {
         rc = CheckImage(out, "out");
         if (rc != OVRFSR_OK) return rc;
-        if (out->width != outputWidth_ || out->height != outputHeight_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
+        if (out->width != plan_.outputWidth || out->height != plan_.outputHeight) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
         dst = canonical(*out);
     } else {
-        dst.width = outputWidth_; dst.height = outputHeight_;
+        dst.width = plan_.outputWidth; dst.height = plan_.outputHeight;
         // an R11G11B10F submission gets what the RGBA16F image of the same values gets (header)
-        dst.format = OwnedFormat(in->format);
+        dst.format = plan_.ownedFormat;
         dst.pitch_bytes = dst.width * texel_bytes(dst.format);
         // (pair mode: both eyes' results are alive at once -- two ctx-owned images, left first)
         const size_t one = (size_t)dst.pitch_bytes * dst.height;
@@ -1100,7 +727,7 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
     // RESOLVED destination -- the caller's buffer or the ctx-owned one: chaining the previous ctx-owned result back in as `in`
     // (sharpen-only mode, where the sizes agree) is the same race
     if (stages && RangesOverlap(*in, 0, dst, 0, 1)) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "input and output images overlap");
-    rc = CheckExactDestination(dst.format);
+    rc = RefuseDisablingDestination(dst.format);
     if (rc != OVRFSR_OK) return rc;
 
     lastApplyRecorded_ = false;
@@ -1158,9 +785,9 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         }
     }
     // a shared side-by-side texture is processed once, on the first Submit (:155-158)
-    if (eyeCount_ == 0 || textureContainsOnlyOneEye_ || in->data != lastSubmittedTexture_) {
+    if (eyeCount_ == 0 || plan_.onlyOneEye || in->data != lastSubmittedTexture_) {
         if (stages) {
-            rc = ApplyPostProcess(1, textureContainsOnlyOneEye_ ? eye : OVRFSR_EYE_LEFT, 0, *in, 0, dst, 0, stream);
+            rc = ApplyPostProcess(1, plan_.onlyOneEye ? eye : OVRFSR_EYE_LEFT, 0, *in, 0, dst, 0, stream);
             if (rc != OVRFSR_OK) return rc;
             outputTexture_ = dst;
         } else {
@@ -1195,20 +822,19 @@ int PostProcessor::ApplyBatch(uint32_t n, int firstEye, int alternate, const ovr
     DeviceGuard guard(device_);
     if (guard.err != hipSuccess) return Fail(OVRFSR_ERR_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
     capturing_ = stream_capturing(stream);
-    if (capturing_ && (!initialized_ || in0->width != inputWidth_ || in0->height != inputHeight_ || in0->format != inputFormat_ || textureContainsOnlyOneEye_ == sharedTextures))
+    if (capturing_ && (!initialized_ || in0->width != plan_.inputWidth || in0->height != plan_.inputHeight || in0->format != plan_.inputFormat || plan_.onlyOneEye == sharedTextures))
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, kCaptureRefusal);
     if (havePending_) { rc = FlushPending(stream); if (rc != OVRFSR_OK) return rc; } // cfg.pair_submit: a recorded LEFT goes first
     // shared side-by-side textures: both mask centres per image, processed once each (PostProcessor.cpp:146,155-158,298-301)
-    if (initialized_ && (in0->width != inputWidth_ || in0->height != inputHeight_ || in0->format != inputFormat_ || textureContainsOnlyOneEye_ == sharedTextures))
+    if (initialized_ && (in0->width != plan_.inputWidth || in0->height != plan_.inputHeight || in0->format != plan_.inputFormat || plan_.onlyOneEye == sharedTextures))
         Reset();
     if (!initialized_) {
-        textureContainsOnlyOneEye_ = !sharedTextures;
-        rc = PrepareResources(*in0);
+        rc = PrepareResources(*in0, !sharedTextures);
         if (rc != OVRFSR_OK) { enabled_ = false; return rc; }
     }
-    if (out0->width != outputWidth_ || out0->height != outputHeight_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
-    if (!(doUpscale_ || doSharpen_)) return Fail(OVRFSR_ERR_UNSUPPORTED, "no stage selected (render_scale == 1 with NIS off would still sharpen)");
-    rc = CheckExactDestination(out0->format);
+    if (out0->width != plan_.outputWidth || out0->height != plan_.outputHeight) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "out has the wrong size");
+    if (!(plan_.doUpscale || plan_.doSharpen)) return Fail(OVRFSR_ERR_UNSUPPORTED, "no stage selected (render_scale == 1 with NIS off would still sharpen)");
+    rc = RefuseDisablingDestination(out0->format);
     if (rc != OVRFSR_OK) return rc;
     return ApplyPostProcess(n, firstEye, alternate, *in0, inStride, *out0, outStride, stream);
 }
@@ -1239,7 +865,7 @@ void PostProcessor::CollectQuery(hipStream_t stream)
     summedGpuTime_ += ms * 1e-3f / (float)(q.images ? q.images : 1u);
     if (++countedQueries_ >= 500) {
         float avgTimeMs = 1000.f / countedQueries_ * summedGpuTime_;
-        if (textureContainsOnlyOneEye_) avgTimeMs *= 2;
+        if (plan_.onlyOneEye) avgTimeMs *= 2;
         avgGpuTimeMs_ = avgTimeMs;
         ++avgReports_;
         static const bool log = [] { const char *e = std::getenv("OVRFSR_LOG"); return e && e[0] == '1'; }();

@@ -9,15 +9,10 @@
 #include "../../include/openvr_fsr_amd.h"
 #include "fsr_params.h"
 #include "nis_tables.h"
+#include "pipeline_plan.h"
 
 namespace ovrfsr {
 
-// host-side constant math (restates FsrEasuCon / FsrRcasCon / NVScalerUpdateConfig; see constants.cpp)
-void easu_con(uint32_t con[16], float inVpW, float inVpH, float inW, float inH, float outW, float outH);
-void rcas_con(uint32_t con[4], float stops);
-void mask_constants(uint32_t centre[4], uint32_t radius[4], uint32_t outW, uint32_t outH, const float proj[4],
-                    float cfgRadius, int onlyOneEye, int eye);
-uint32_t classify_mask(const uint32_t centre[4], uint32_t r2, uint32_t outW, uint32_t outH, uint32_t gw, uint32_t gh);
 #ifdef OVRFSR_BOUNDS
 void debug_fail_resource(int nth); // checked builds: the nth device allocation / stream / event creation from now on fails, once (postprocessor.cpp)
 #endif
@@ -55,46 +50,20 @@ private:
     // PostProcessor.h:16-24
     bool enabled_ = true;
     bool initialized_ = false;
-    uint32_t inputWidth_ = 0, inputHeight_ = 0, outputWidth_ = 0, outputHeight_ = 0;
-    uint32_t inputFormat_ = 0;
-    bool textureContainsOnlyOneEye_ = true;
     // PostProcessor.h:66-68
     const void *lastSubmittedTexture_ = nullptr;
     ovrfsr_image outputTexture_ = {};
     int eyeCount_ = 0;
 
-    // stage selection, PostProcessor.cpp:530-535 / :586-594
-    bool doUpscale_ = false, doSharpen_ = false;
-
-    // "constant buffers", one per eye: PostProcessor.cpp:296-338, :419-460
-    uint32_t easuCon_[16] = {};
-    uint32_t rcasCon_[4] = {};
-    uint32_t centre_[2][4] = {};
-    uint32_t radius_[4] = {};
-    uint32_t maskMode_[2] = {};
-    uint32_t outsideCols_ = 0, outsideRows_[2] = {0, 0}; // bilinear footprint bound of a 32-wide tile; rows for 32- and 24-row tiles
-    float rcpOut_[2] = {0, 0}; // RN(1/outW), RN(1/outH) and whether mul+2fma reproduces o/out for every o (div_exact)
-    bool rcpExact_ = false;
-    int cellsW_ = 0, cellsH_ = 0;
-    int fusedCellsW_ = 0, fusedCellsH_ = 0; // footprint of the 34x34 EASU block of the fused kernel
-    bool useFused_ = false;
-    // NIS: the 256-byte NISConfig (PostProcessor.cpp:307-310) and the coefficient "textures" (:366-381)
-    NisConstants nisConfig_ = {};
-    float *nisCoefDev_ = nullptr; // coef_scale[512] | coef_usm[512]
-    BilinTap *bilinDev_ = nullptr; // [outW] column taps (padded to a multiple of the tile width with copies of the last one), then [outH] row taps at bilYOff_
-    uint32_t bilYOff_ = 0;
-    // mask-sorted EASU tile lists (product build, masked configs): per eye, tiles with any group inside the radius
-    // and tiles entirely outside; the latter run through an LDS-free kernel at twice the occupancy
-    uint32_t *tileListDev_ = nullptr;
-    uint32_t *tileRecDev_ = nullptr;      // records of the same entries (inside the tileListDev_ allocation), 4 dwords each
-    uint32_t *spanRecDev_ = nullptr;      // RCAS segments of the inside runs (inside the tileListDev_ allocation), 2 dwords each
-    uint32_t nSpans_[2] = {0, 0};
-    size_t spanOff_[2] = {0, 0};          // first segment of each eye (in segments)
-    std::vector<BilinTap> bilinHost_;     // host copy of the column / row tap tables (bilinDev_)
-    uint32_t nInside_[2] = {0, 0}, nOutside_[2] = {0, 0}, nRing_[2] = {0, 0};
-    size_t listOffInside_[2] = {0, 0}, listOffOutside_[2] = {0, 0}, listOffRing_[2] = {0, 0}; // ring: outside tiles 4-adjacent to an inside tile
-    bool useSorted_ = false;   // masked EASU+RCAS: two passes on the inside list, final-form outside tiles (ApplySorted)
-    bool listsShared_ = false; // both eyes have identical lists
+    // What the ctx does for the current (configuration, submitted format, size): decided on the host (pipeline_plan.h), read by every
+    // per-call helper.  A Reset replaces it with a fresh one.
+    Plan plan_;
+    // the plan's tables on the device (PrepareResources uploads them, in this order)
+    float *nisCoefDev_ = nullptr;         // coef_scale[512] | coef_usm[512] (PostProcessor.cpp:366-381)
+    BilinTap *bilinDev_ = nullptr;        // Plan::taps
+    uint32_t *tileListDev_ = nullptr;     // Plan::lists, then inside the same allocation:
+    uint32_t *tileRecDev_ = nullptr;      //   Plan::recs, 4 dwords per list entry
+    uint32_t *spanRecDev_ = nullptr;      //   Plan::spans, 2 dwords per segment
     // the memory-bound outside-tile kernel and the VALU-bound inside-tile kernel are independent: the former runs on
     // a ctx-owned auxiliary stream, forked from and joined back into the caller's stream with events
     hipStream_t auxStream_ = nullptr;
@@ -111,10 +80,8 @@ private:
     DeviceBuffer retired_;    // a ctx-owned output image a flushed pair_submit eye was handed in, kept across the rebuild of a size change
     void ResetKeeping(bool keepRetired);
     int FlushPending(hipStream_t stream);
-    bool OverlapOutside(const ovrfsr_image &in) const; // does a masked pass run its outside-tile kernel on the auxiliary stream?
     hipStream_t Fork(hipStream_t user, bool overlap);
     void Join(hipStream_t user, hipStream_t aux);
-    int nisCellsW_ = 0, nisCellsH_ = 0;
 
     // ctx-owned device buffers: upscaledTexture / sharpenedTexture, PostProcessor.h:43-45,58-59
     DeviceBuffer swizzled_;  // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
@@ -137,10 +104,7 @@ private:
 
     int Fail(int status, const std::string &what);
     int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled / R11G11B10F
-    int PrepareResources(const ovrfsr_image &in);                         // :498-561
-    void PrepareUpscalingResources();                                    // :285-383
-    void PrepareSharpeningResources();                                   // :409-481
-    int PrepareTileLists(uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH);
+    int PrepareResources(const ovrfsr_image &in, bool onlyOneEye);        // :498-561: plan (pipeline_plan.h), then upload
     // one masked launch round: images first, first + step, ... (cnt of them) of the batch, all of eye `eye` when `split`
     struct EyePass {
         int eye; uint32_t cnt, first, step; bool split;
@@ -148,22 +112,16 @@ private:
     };
     int EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const;
     // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text
-    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, hipStream_t stream, const char *what, Body body);
+    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, const char *what, Body body);
     int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
     template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     void FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     void FillEasu(EasuArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
-    int PrepareNisResources();                                           // :307-310, :366-382, :432-435
     void FillNis(NisArgs &a, int firstEye, int alternate) const;
     int EnsureBuffer(DeviceBuffer &buf, size_t need);
     int IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride); // the upscale stage's destination in front of a sharpening stage
     static bool RangesOverlap(const ovrfsr_image &in0, size_t inStride, const ovrfsr_image &out0, size_t outStride, uint32_t n);
-    int LaunchPrec() const;
-    bool ProductArithmetic() const;
-    int CheckExactDestination(uint32_t format);
-    uint32_t IntermediateFormat() const;
-    uint32_t OwnedFormat(uint32_t submitted) const;
-    bool ResolveInStaging(const ovrfsr_image &in, const ovrfsr_image &out) const;
+    int RefuseDisablingDestination(uint32_t format);
     float TieHalfMin() const;
     int ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
                          const ovrfsr_image &out, size_t outStride, hipStream_t stream); // :563-638

@@ -8,7 +8,14 @@ measures that ceiling: calls per second the host can issue, on images so small (
 is a few microseconds.  All threads target device 0 (a gpurun box has one GPU): the host path is the same as with one
 device per thread, and the device never becomes the bottleneck before the host does at these sizes.
 The torchrun launcher (what the round driver uses for N > 1) has one process, hence one GIL, per GPU: there the
-single-thread row applies."""
+single-thread row applies.
+
+    python tools/debug/host_enqueue.py --c2
+One thread, C2's shape (1683x1869 -> 2244x2492), ONE EYE PER CALL through PostProcessor.apply -- the reference's call pattern -- unmasked
+(radius 2.0: two-pass) and masked (radius 0.5: mask-sorted): host time per call (400 calls, the queue drained every 8), and the wall time
+of the first apply of a fresh ctx, synchronised (plan + upload + launch: the rebuild; median of 8 fresh ctxs, the process's first one
+discarded because it loads the code objects).  Prints one line "C2 {json}".  OVRFSR_LIB selects the library, so two builds can be run
+alternately, one process per run (profiles/pipeline_plan.txt)."""
 import os
 import sys
 import threading
@@ -44,6 +51,45 @@ def worker(i, gate, out):
         out[i] = (t1 - t0) / CALLS
         pp.close()
 
+
+def c2_single_eye():
+    import json
+    iw, ih, ow, oh = 1683, 1869, 2244, 2492
+    tex = [torch.randint(0, 255, (ih, iw, 4), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    out = [torch.empty((oh, ow, 4), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    res = {}
+    for name, radius in (("unmasked", 2.0), ("masked", 0.5)):
+        cfg = dict(fsr_enabled=1, out_width=ow, out_height=oh, sharpness=0.9, radius=radius)
+        firsts = []
+        for _ in range(9):
+            pp = A.PostProcessor(**cfg)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pp.apply(0, tex[0], out=out[0])
+            torch.cuda.synchronize()
+            firsts.append((time.perf_counter() - t0) * 1e3)
+            pp.close()
+        res["first_apply_ms_" + name] = sorted(firsts[1:])[len(firsts[1:]) // 2]
+        pp = A.PostProcessor(**cfg)
+        for k in range(20):
+            pp.apply(k & 1, tex[k & 1], out=out[k & 1])
+        torch.cuda.synchronize()
+        calls, host = 400, 0.0
+        for k in range(calls):
+            t0 = time.perf_counter()
+            pp.apply(k & 1, tex[k & 1], out=out[k & 1])
+            host += time.perf_counter() - t0
+            if (k & 7) == 7:
+                torch.cuda.synchronize()   # keep the launch queue shallow
+        torch.cuda.synchronize()
+        res["host_us_per_call_" + name] = host / calls * 1e6
+        pp.close()
+    print("C2 " + json.dumps(res), flush=True)
+
+
+if "--c2" in sys.argv[1:]:
+    c2_single_eye()
+    sys.exit(0)
 
 print("threads  us_per_call(mean over threads)  calls_per_s(all threads)   [EASU + RCAS apply_batch of 2 images 24x24 -> 32x32, %d calls per thread]" % CALLS)
 for n in (1, 2, 4, 8):
