@@ -234,6 +234,44 @@ static bool rcas_dpp_small(const RcasArgs &a, uint32_t batch)
     return wgs < 16 * kRcasResident && 103 * half < 200 * full;
 }
 
+// The fast RCAS kernels of an RGBA8 source, as two sets with the same three members: the plain instances by destination format, and the
+// guarded exact-stores instances (RGBA8 -> RGBA8 only).
+template <int O>
+struct RcasPlainSet {
+    template <bool SPANS, int TH> static constexpr auto dpp() { return &ovrfsr_fast::rcas_dpp_kernel<O, SPANS, TH>; }
+    static constexpr auto direct() { return &ovrfsr_fast::rcas_direct_kernel<FMT_RGBA8, O>; }
+};
+struct RcasExactSet {
+    template <bool SPANS, int TH> static constexpr auto dpp() { return &ovrfsr_fast::rcas_dpp_exact_kernel<SPANS, TH>; }
+    static constexpr auto direct() { return &ovrfsr_fast::rcas_direct_exact_kernel; }
+};
+
+// The form of a fast RCAS launch from an RGBA8 image, one rule for both sets: the DPP kernel on whole rows of 32- or 16-row workgroups
+// (unmasked), on the span records of a mask-sorted launch, or the per-lane-loads kernel on `grid`.
+template <class Set>
+static void rcas_fast_go(bool dpp, const RcasArgs &a, dim3 grid, hipStream_t s)
+{
+    const bool unmasked = !a.tileList && a.m.mode[0] == MASK_ALL_INSIDE && a.m.mode[1] == MASK_ALL_INSIDE;
+    if (dpp && unmasked) {
+        const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
+        // small launches: the grid is r = workgroups / kRcasResident rounds of the resident workgroups, the last one partly filled;
+        // half-height workgroups run ceil(2r) rounds of half the length (3 % more work per pixel).  One C2 eye image: r = 1.41,
+        // 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us, profiles/r05_frame.txt); a batch: no difference, the
+        // 8-row form wins
+        if (rcas_dpp_small(a, grid.z)) {
+            const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
+            hipLaunchKernelGGL((Set::template dpp<false, 16>()), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((Set::template dpp<false, kRcasDppTileH>()), dim3(tx * ty, 1, grid.z), dim3(kThreads), 0, s, a);
+        }
+    } else if (dpp && a.tileList && a.spanRec && a.nSpans) {
+        // mask-sorted form: the DPP kernel on 62-column segments of the runs of tiles touching the radius
+        hipLaunchKernelGGL((Set::template dpp<true, kRcasDppTileH>()), dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((Set::direct()), grid, dim3(kThreads), 0, s, a);
+    }
+}
+
 template <int I, int O>
 static hipError_t rcas_go(bool strict, bool exact, const RcasArgs &a, dim3 grid, hipStream_t s)
 {
@@ -242,48 +280,14 @@ static hipError_t rcas_go(bool strict, bool exact, const RcasArgs &a, dim3 grid,
 #else
     constexpr bool dpp = true;
 #endif
-    const bool unmasked = !a.tileList && a.m.mode[0] == MASK_ALL_INSIDE && a.m.mode[1] == MASK_ALL_INSIDE;
     if (strict) {
         hipLaunchKernelGGL((ovrfsr_strict::rcas_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
     } else if (exact) {
-        // exact stores: the same three forms, chosen by the same rules, on the guarded RGBA8 -> RGBA8 instances; no other pair has any
-        if constexpr (I == FMT_RGBA8 && O == FMT_RGBA8) {
-            if (unmasked) {
-                const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW;
-                if (rcas_dpp_small(a, grid.z)) {
-                    const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
-                    hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<false, 16>), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
-                } else {
-                    const uint32_t ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
-                    hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<false, kRcasDppTileH>), dim3(tx * ty, 1, grid.z), dim3(kThreads), 0, s, a);
-                }
-            } else if (a.tileList && a.spanRec && a.nSpans) {
-                hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_exact_kernel<true, kRcasDppTileH>), dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
-            } else {
-                hipLaunchKernelGGL(ovrfsr_fast::rcas_direct_exact_kernel, grid, dim3(kThreads), 0, s, a);
-            }
-        } else {
-            return hipErrorInvalidValue;
-        }
+        // exact stores: the guarded RGBA8 -> RGBA8 instances; no other pair has any
+        if constexpr (I == FMT_RGBA8 && O == FMT_RGBA8) rcas_fast_go<RcasExactSet>(true, a, grid, s);
+        else return hipErrorInvalidValue;
     } else if constexpr (I == FMT_RGBA8 && O != FMT_RGB10A2) {
-        if (dpp && unmasked) {
-            const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
-            // small launches: the grid is r = workgroups / kRcasResident rounds of the resident workgroups, the last one partly filled;
-            // half-height workgroups run ceil(2r) rounds of half the length (3 % more work per pixel).  One C2 eye image: r = 1.41,
-            // 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us, profiles/r05_frame.txt); a batch: no difference, the
-            // 8-row form wins
-            if (rcas_dpp_small(a, grid.z)) {
-                const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
-                hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_kernel<O, false, 16>), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
-            } else {
-                hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_kernel<O>), dim3(tx * ty, 1, grid.z), dim3(kThreads), 0, s, a);
-            }
-        } else if (dpp && a.tileList && a.spanRec && a.nSpans) {
-            // mask-sorted form: the DPP kernel on 62-column segments of the runs of tiles touching the radius
-            hipLaunchKernelGGL((ovrfsr_fast::rcas_dpp_kernel<O, true>), dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
-        } else {
-            hipLaunchKernelGGL((ovrfsr_fast::rcas_direct_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
-        }
+        rcas_fast_go<RcasPlainSet<O>>(dpp, a, grid, s);
     } else {
         hipLaunchKernelGGL((ovrfsr_fast::rcas_direct_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
     }

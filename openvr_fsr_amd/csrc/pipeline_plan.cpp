@@ -301,6 +301,14 @@ const char *form_name(Form f)
     return names[(int)f];
 }
 
+// UNORM8 store of a float source (easu_fast_kernel<RGBA16F / RGBA32F, RGBA8>: the kernel has no half store, so the field is its guard's
+// SWITCH): +inf = off, the stores of every earlier release; finite = on, the store is the strict build's bit for bit.
+float easu_tie_half_min(const Plan &plan, uint32_t inFormat, uint32_t outFormat, float halfGuard)
+{
+    const bool floatToUnorm8 = (inFormat == OVRFSR_FORMAT_RGBA16F || inFormat == OVRFSR_FORMAT_RGBA32F) && outFormat == OVRFSR_FORMAT_RGBA8_UNORM;
+    return floatToUnorm8 ? plan.unorm8StoreGuard : halfGuard;
+}
+
 int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint32_t *outW, uint32_t *outH)
 {
     constexpr uint32_t kMaxExtent = 16384; // same limit CheckImage puts on caller images
@@ -395,6 +403,8 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
         p.rcasCon[3] = cfg.debug_mode ? 1u : 0u; // :430
     }
     p.tieHalfMin = tie_half_min(cfg, p);
+    // on exactly under cfg.reference_formats -- the pipeline's UNORM8 intermediate and an EASU-only RGBA8 output alike
+    p.unorm8StoreGuard = cfg.reference_formats ? 0.0f : INFINITY;
 
     // The form.  One launch with the intermediate in LDS only on request: on this chip both stages are VALU-bound and the ring
     // recompute costs more than the HBM round trip saves, so auto (-1) means two kernels.

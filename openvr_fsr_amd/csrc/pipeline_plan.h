@@ -66,6 +66,7 @@ struct Plan {
     uint32_t radius[4] = {};
     uint32_t maskMode[2] = {};
     float tieHalfMin = 0.0f;     // near-tie guard of a half intermediate (plan_pipeline); +inf = off
+    float unorm8StoreGuard = 0.0f; // guard SWITCH of EASU's UNORM8 store of a float source (easu_tie_half_min): +inf = off, finite = on
     int cellsW = 0, cellsH = 0;           // LDS footprint of one EASU tile
     int fusedCellsW = 0, fusedCellsH = 0; // ... of the 34x34 EASU block of the fused kernel
     int nisCellsW = 0, nisCellsH = 0;     // ... of one 32x24 NVScaler group
@@ -92,6 +93,9 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
 
 // what depends on the destination the call names
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat);
+// EasuArgs::tieHalfMin of one EASU launch from inFormat into outFormat.  `halfGuard`: the guard of a half store (Plan::tieHalfMin, or the
+// override an audit build puts in its place).
+float easu_tie_half_min(const Plan &plan, uint32_t inFormat, uint32_t outFormat, float halfGuard);
 // a 4-sample RGBA8 submission resolved inside EASU's staging sweep instead of the resolve pass
 bool resolve_in_staging(const Plan &plan, uint32_t destFormat);
 

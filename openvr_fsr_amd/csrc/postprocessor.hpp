@@ -10,6 +10,7 @@
 #include "fsr_params.h"
 #include "nis_tables.h"
 #include "pipeline_plan.h"
+#include "submit_sequence.h"
 
 namespace ovrfsr {
 
@@ -23,6 +24,7 @@ struct DeviceBuffer {
     size_t bytes = 0;
     void release();
 };
+struct DeviceGuard; // hipSetDevice for the duration of a call (postprocessor.cpp)
 
 class PostProcessor {
 public:
@@ -38,7 +40,7 @@ public:
     int SetConfig(const ovrfsr_config &cfg);
     const ovrfsr_config &GetConfig() const { return cfg_; }
     const char *LastError() const { return lastError_.c_str(); }
-    bool PairPending() const { return lastApplyRecorded_ && havePending_; }
+    bool PairPending() const { return sequence_.PairPending(); }
     int LastGpuTimeMs(float *ms);
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
@@ -50,10 +52,9 @@ private:
     // PostProcessor.h:16-24
     bool enabled_ = true;
     bool initialized_ = false;
-    // PostProcessor.h:66-68
-    const void *lastSubmittedTexture_ = nullptr;
-    ovrfsr_image outputTexture_ = {};
-    int eyeCount_ = 0;
+    // what each Apply does with its submission -- the reference's Submit bookkeeping (PostProcessor.h:66-68) and the deferred pair of
+    // cfg.pair_submit: decided on the host (submit_sequence.h); Apply launches what it is told
+    SubmitSequencer sequence_;
 
     // What the ctx does for the current (configuration, submitted format, size): decided on the host (pipeline_plan.h), read by every
     // per-call helper.  A Reset replaces it with a fresh one.
@@ -68,18 +69,18 @@ private:
     // a ctx-owned auxiliary stream, forked from and joined back into the caller's stream with events
     hipStream_t auxStream_ = nullptr;
     hipEvent_t evFork_ = nullptr, evJoin_ = nullptr;
-    // cfg.pair_submit: the recorded FIRST submission of the current frame (either eye; see the header) and what it takes to launch it
-    bool havePending_ = false;
-    int pendingEye_ = 0;
-    int pairFirstEye_ = -1;          // the eye that opens a frame, learned from the last completed pair (-1: not known yet)
-    bool pairDefer_ = true;          // false after the same eye came twice in a row, until the other eye is seen again
-    int lastEye_ = -1;
-    bool lastApplyRecorded_ = false; // the last Apply only recorded its submission (ovrfsr_pair_pending)
-    bool capturing_ = false;         // the stream of the call in progress is being captured into a HIP graph: launches only, no (re)build
-    ovrfsr_image pendingIn_{}, pendingOut_{};
+    bool capturing_ = false;  // the stream of the call in progress is being captured into a HIP graph: launches only, no (re)build
     DeviceBuffer retired_;    // a ctx-owned output image a flushed pair_submit eye was handed in, kept across the rebuild of a size change
     void ResetKeeping(bool keepRetired);
-    int FlushPending(hipStream_t stream);
+    int FlushPending(hipStream_t stream, bool *ownedOutput = nullptr); // the recorded submission of cfg.pair_submit on its own, if there is one
+    // What Apply and ApplyBatch do before they look at the destination: device, capture refusal, "is the plan still for this input", reset,
+    // PrepareResources.  Their two deliberate differences are the last two arguments.
+    enum class Recorded {
+        GoesFirst,   // ApplyBatch: a recorded eye is launched before the size is looked at
+        OnChange     // Apply: only where the plan changes, and a ctx-owned image it was handed in is retired, not freed
+    };
+    int EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout, Recorded recorded, hipStream_t stream);
+    bool PlannedFor(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const;
     hipStream_t Fork(hipStream_t user, bool overlap);
     void Join(hipStream_t user, hipStream_t aux);
 
@@ -113,6 +114,14 @@ private:
     int EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const;
     // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text
     template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, const char *what, Body body);
+    // one pass's two launches: `inside` with the list of the tiles touching the radius (+ `ring` tiles behind them) on the caller's stream,
+    // then `outside` with the list and records of the other tiles on the auxiliary one
+    template <class In, class Out, class LaunchIn, class LaunchOut>
+    hipError_t InsideThenOutside(const EyePass &ps, In inside, Out outside, uint32_t ring, LaunchIn launchInside, LaunchOut launchOutside) const;
+    const uint32_t *InsideList(int eye) const { return tileListDev_ + plan_.listOffInside[eye]; }
+    const uint32_t *OutsideList(int eye) const { return tileListDev_ + plan_.listOffOutside[eye]; }
+    const uint32_t *OutsideRecords(int eye) const { return tileRecDev_ + 4 * plan_.listOffOutside[eye]; }
+    const uint32_t *SpanRecords(int eye) const { return spanRecDev_ + 2 * plan_.spanOff[eye]; }
     int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
     template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     void FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
@@ -120,7 +129,6 @@ private:
     void FillNis(NisArgs &a, int firstEye, int alternate) const;
     int EnsureBuffer(DeviceBuffer &buf, size_t need);
     int IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride); // the upscale stage's destination in front of a sharpening stage
-    static bool RangesOverlap(const ovrfsr_image &in0, size_t inStride, const ovrfsr_image &out0, size_t outStride, uint32_t n);
     int RefuseDisablingDestination(uint32_t format);
     float TieHalfMin() const;
     int ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,

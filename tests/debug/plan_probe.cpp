@@ -6,8 +6,10 @@
 //       id format width height onlyOneEye destFormat(-1: ctx-owned) fsr_enabled use_nis debug_mode render_scale sharpness radius
 //       proj_centre[4] out_width out_height precision quantize_intermediate fused stage_mask pair_submit reference_formats
 //   Each line reports the refusal or the plan (form, formats, stage selection, list sizes), the destination refusal and resolve_in_staging
-//   for the destination, and "invariants": "ok" or the first structural invariant of the plan's tables that does not hold.
+//   for the destination, "unorm8_guard" (is the guard of an EASU launch from the pipeline format into RGBA8 switched on: easu_tie_half_min),
+//   and "invariants": "ok" or the first structural invariant of the plan's tables that does not hold.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -151,11 +153,12 @@ int main(int argc, char **argv)
             const Refusal dr = destination_refusal(p, d);
             std::printf(", \"form\": %s, \"out\": [%u, %u], \"upscale\": %d, \"sharpen\": %d, \"pipeline\": %u, \"mid\": %u, \"owned\": %u, \"tile_lists\": %d, "
                         "\"overlap\": %d, \"lists_shared\": %d, \"dest_status\": %d, \"dest_text\": %s, \"dest_disables\": %d, \"resolve_in_staging\": %d, "
-                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"invariants\": %s",
+                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"unorm8_guard\": %d, \"invariants\": %s",
                         quoted(form_name(p.form)).c_str(), p.outputWidth, p.outputHeight, (int)p.doUpscale, (int)p.doSharpen, p.pipelineFormat,
                         p.intermediateFormat, p.ownedFormat, (int)p.tileLists, (int)p.overlapOutside, (int)p.listsShared, dr.status, quoted(dr.text).c_str(),
                         (int)dr.disables, (int)resolve_in_staging(p, d), p.nInside[0], p.nInside[1], p.nRing[0], p.nRing[1], p.nOutside[0], p.nOutside[1],
-                        p.nSpans[0], p.nSpans[1], quoted(invariants(p, c.use_nis != 0).c_str()).c_str());
+                        p.nSpans[0], p.nSpans[1], (int)std::isfinite(easu_tie_half_min(p, p.pipelineFormat, OVRFSR_FORMAT_RGBA8_UNORM, INFINITY)),
+                        quoted(invariants(p, c.use_nis != 0).c_str()).c_str());
         }
         std::printf("}\n");
     }

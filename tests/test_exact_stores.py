@@ -1,16 +1,15 @@
 """OVRFSR_PRECISION_FP32_EXACT (exact stores), the parts that need no GPU: the public value and its probe, the guarded RCAS instances in the
 code object, the fingerprint record, and the tie-rich fixture the GPU tests stand on (tests/rcas_ties.py)."""
 import ctypes as C
-import json
 import os
 
 import openvr_fsr_amd as A
 from openvr_fsr_amd import _capi as K
+from tests import isa
 from tests.test_kernel_resources import kernels  # noqa: F401  (the code-object fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FP_NOW = os.path.join(ROOT, "profiles", "r06_isa_fingerprint_r06.json")
-FP_BEFORE = os.path.join(ROOT, "profiles", "exact_stores_fingerprint_before.json")
+FP_NOW, FP_BEFORE = "r06_isa_fingerprint_r06.json", "exact_stores_fingerprint_before.json"   # (records under profiles/: tests/isa.py)
 # mangled-name fragments of the guarded instances: rcas_dpp_exact_kernel<SPANS, TH> and rcas_direct_exact_kernel
 EXACT_KERNELS = ("21rcas_dpp_exact_kernelILb0ELi32E", "21rcas_dpp_exact_kernelILb0ELi16E", "21rcas_dpp_exact_kernelILb1ELi32E", "24rcas_direct_exact_kernel")
 EXACT_NAMES = ("void ovrfsr_fast::rcas_dpp_exact_kernel<false, 32>(ovrfsr::RcasArgs)", "void ovrfsr_fast::rcas_dpp_exact_kernel<false, 16>(ovrfsr::RcasArgs)",
@@ -53,7 +52,7 @@ def test_guarded_rcas_instances_exist_and_stay_in_registers(kernels):  # noqa: F
 
 
 def test_fingerprint_lists_the_new_kernels_and_keeps_every_old_hash():
-    now, before = json.load(open(FP_NOW)), json.load(open(FP_BEFORE))
+    now, before = isa.record(FP_NOW), isa.record(FP_BEFORE)
     for name in EXACT_NAMES:
         assert name in now and name not in before, name
     assert sorted(set(now) - set(before)) == sorted(EXACT_NAMES)

@@ -1,6 +1,5 @@
 """Multisampled inputs (OVRFSR_FORMAT_MS), the parts that need no GPU: the resolve rule's known answers, the resolve kernels' resources,
 the shipped kernels' machine code, the header encoding and the Python descriptors."""
-import json
 import os
 import subprocess
 
@@ -8,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import msaa
+from tests import isa, msaa
 from tests.test_kernel_resources import _alloc, kernels  # noqa: F401  (the code-object fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,12 +139,8 @@ def test_shipped_kernels_are_unchanged():
     the only additions are the resolve kernels and the 4-sample RGBA8 instances of easu_fast_kernel."""
     if not os.path.exists(LIB):
         pytest.fail("libopenvr_fsr_amd.so is not built: run __graft_entry__.build()")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("isa_fingerprint", os.path.join(ROOT, "tools", "isa_fingerprint.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    now = mod.fingerprint(LIB)
-    base = json.load(open(os.path.join(ROOT, "profiles", "r06_isa_fingerprint_r06.json")))
+    now = isa.fingerprint_of_built_library()
+    base = isa.record("r06_isa_fingerprint_r06.json")
     changed = sorted(k for k in base if now.get(k) != base[k])
     assert not changed, changed
     added = sorted(set(now) - set(base))

@@ -1,7 +1,6 @@
 """R11G11B10F inputs (OVRFSR_FORMAT_R11G11B10F), the parts that need no GPU: the decode rule against the format's definition for every
 code, the multisample rule on packed samples, the unpack kernels' presence and resources, the shipped kernels' machine code, the header
 and the Python descriptors."""
-import json
 import os
 import subprocess
 
@@ -9,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import msaa, packedf
+from tests import isa, msaa, packedf
 from tests.test_kernel_resources import _alloc, kernels  # noqa: F401  (the code-object fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,22 +111,14 @@ def test_unpack_kernels_budget(kernels):  # noqa: F811
         assert _alloc(v["vgpr_count"]) <= 64, (k, v["vgpr_count"])
 
 
-def _fingerprint_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("isa_fingerprint", os.path.join(ROOT, "tools", "isa_fingerprint.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_only_the_unpack_kernels_are_added():
     """Against the last recorded fingerprint every listed kernel keeps its machine code, and against the one recorded with this format
     (which lists the multisample kernels too) nothing changed and nothing is missing or extra: the additions of this format are exactly
     the four packed_resolve_kernel instances."""
     if not os.path.exists(LIB):
         pytest.fail("libopenvr_fsr_amd.so is not built: run __graft_entry__.build()")
-    now = _fingerprint_module().fingerprint(LIB)
-    r06 = json.load(open(os.path.join(ROOT, "profiles", "r06_isa_fingerprint_r06.json")))
+    now = isa.fingerprint_of_built_library()
+    r06 = isa.record("r06_isa_fingerprint_r06.json")
     assert not sorted(k for k in r06 if now.get(k) != r06[k])
     added = sorted(set(now) - set(r06))
     mine = [k for k in added if "packed_resolve_kernel" in k]
@@ -135,7 +126,7 @@ def test_only_the_unpack_kernels_are_added():
     rest = [k for k in added if k not in mine]
     assert len(rest) == 18 and all(k.startswith("void ovrfsr_fast::resolve_kernel<") or k.startswith("void ovrfsr_fast::easu_fast_kernel<1024,")
                                    for k in rest), rest
-    rec = json.load(open(os.path.join(ROOT, "profiles", "r11g11b10f_isa_fingerprint.json")))
+    rec = isa.record("isa_fingerprint.json")
     assert sorted(rec) == sorted(now)
     assert not sorted(k for k in rec if now[k] != rec[k])
 

@@ -14,6 +14,8 @@ import tempfile
 
 import pytest
 
+from tests import isa
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "openvr_fsr_amd", "csrc")
 
@@ -109,10 +111,10 @@ FORM_TABLE = [
     _named("MS4 RGBA8 unmasked, EASU only into float", MS4_RGBA8, MATRIX, dict(form="upscale only", resolve_in_staging=0), dest=RGBA32F, radius=2.0, stage_mask=1),
     _named("MS4 RGBA8 unmasked, strict", MS4_RGBA8, MATRIX, dict(form="two-pass", resolve_in_staging=0), radius=2.0, precision=2),
     # a float source under reference_formats: UNORM8 intermediate and output, mask-sorted where there is a mask, in order on the caller's stream
-    _named("RGBA16F reference_formats masked", RGBA16F, MATRIX, dict(form="mask-sorted", mid=RGBA8, owned=RGBA8, overlap=0), reference_formats=1, **M),
+    _named("RGBA16F reference_formats masked", RGBA16F, MATRIX, dict(form="mask-sorted", mid=RGBA8, owned=RGBA8, overlap=0, unorm8_guard=1), reference_formats=1, **M),
     _named("R11G11B10F reference_formats masked", R11G11B10F, MATRIX, dict(form="mask-sorted", pipeline=RGBA16F, mid=RGBA8, owned=RGBA8), reference_formats=1, **M),
     _named("RGBA16F reference_formats unmasked", RGBA16F, MATRIX, dict(form="two-pass", mid=RGBA8, owned=RGBA8), reference_formats=1, radius=2.0),
-    _named("RGBA16F own formats masked", RGBA16F, MATRIX, dict(form="fused with masked outside tiles", mid=RGBA16F, owned=RGBA16F), **M),
+    _named("RGBA16F own formats masked", RGBA16F, MATRIX, dict(form="fused with masked outside tiles", mid=RGBA16F, owned=RGBA16F, unorm8_guard=0), **M),
     # FP32_EXACT: the two-pass and mask-sorted forms only (and the stages on their own)
     _named("FP32_EXACT unmasked", RGBA8, MATRIX, dict(form="two-pass"), precision=3, radius=2.0),
     _named("FP32_EXACT masked", RGBA8, MATRIX, dict(form="mask-sorted"), precision=3, **M),
@@ -294,12 +296,9 @@ def test_table_invariants_largest_output(probe):
 
 # ---- machine code unmoved -----------------------------------------------------------------------------------------------------------
 def test_fingerprint_unmoved():
-    """the planner is a host refactor: against the parent commit's build (profiles/pipeline_plan_fingerprint_before.json) the library holds the
-    same kernels, every one with the same machine code"""
-    spec = importlib.util.spec_from_file_location("isa_fingerprint", os.path.join(ROOT, "tools", "isa_fingerprint.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    now = mod.fingerprint(os.path.join(ROOT, "openvr_fsr_amd", "libopenvr_fsr_amd.so"))
-    before = json.load(open(os.path.join(ROOT, "profiles", "pipeline_plan_fingerprint_before.json")))
+    """the planner and what followed it are host refactors: against the record of the current library (profiles/isa_fingerprint.json, unchanged
+    since the planner's parent commit) the library holds the same kernels, every one with the same machine code"""
+    now = isa.fingerprint_of_built_library()
+    before = isa.record("isa_fingerprint.json")
     assert set(now) == set(before), sorted(set(now) ^ set(before))
     assert [k for k in before if now[k] != before[k]] == []

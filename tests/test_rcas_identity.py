@@ -9,12 +9,13 @@ Checked here without a GPU, over all 32 896 pairs of byte extrema (P = 255):
   * the scope of the re-recorded machine-code fingerprints: only the byte-domain RCAS kernels changed, and easu_fast_kernel (the pair
     resolve's shared dering extrema, part of the same change).
 tests/test_gpu_rcas_identity.py repeats the comparison on the device with the real v_rcp_f32 and the shipped helper."""
-import json
 import os
 import re
 from fractions import Fraction
 
 import numpy as np
+
+from tests import isa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 255
@@ -100,13 +101,12 @@ CHANGED_FAMILIES = (
 )
 
 
-def _record(name):
-    return json.load(open(os.path.join(ROOT, "profiles", name)))
+_record = isa.record
 
 
 def test_fingerprint_scope():
     before = _record("rcas_one_quotient_fingerprint_before.json")
-    after = _record("r11g11b10f_isa_fingerprint.json")
+    after = _record("isa_fingerprint.json")
     assert sorted(before) == sorted(after)
     changed = sorted(k for k in before if before[k] != after[k])
     assert changed, "the one-quotient form must have changed the byte-domain RCAS kernels"

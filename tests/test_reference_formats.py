@@ -1,7 +1,6 @@
 """cfg.reference_formats (the reference's DetermineOutputFormat rule as an opt-in), the parts that need no GPU: the header and the ctypes
 mirror, the validation, the six new outside-tile kernels and the guarded EASU instances' resources, and the scope of the machine-code change."""
 import ctypes as C
-import json
 import os
 import re
 import subprocess
@@ -9,6 +8,7 @@ import subprocess
 import pytest
 
 import openvr_fsr_amd as A
+from tests import isa
 from tests.test_kernel_resources import _alloc, kernels  # noqa: F401  (the code-object fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,12 +111,8 @@ def test_guarded_easu_instances_stay_inside_the_half_store_forms_budget(kernels)
 def test_fingerprint_scope():
     """Against the parent commit's build (profiles/reference_formats_fingerprint_before.json) the library differs in exactly the twelve
     guarded easu_fast_kernel instances and the six new outside-tile kernels; no other kernel's machine code moved."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("isa_fingerprint", os.path.join(ROOT, "tools", "isa_fingerprint.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    now = mod.fingerprint(os.path.join(ROOT, "openvr_fsr_amd", "libopenvr_fsr_amd.so"))
-    before = json.load(open(os.path.join(ROOT, "profiles", "reference_formats_fingerprint_before.json")))
+    now = isa.fingerprint_of_built_library()
+    before = isa.record("reference_formats_fingerprint_before.json")
     added = sorted(set(now) - set(before))
     assert not set(before) - set(now)
     assert added == ["void ovrfsr_fast::easu_outside_kernel<%d, %d, 0>(ovrfsr::EasuArgs)" % (i, o) for i in (1, 2) for o in (0, 1, 2)], added
@@ -124,7 +120,7 @@ def test_fingerprint_scope():
     want = sorted("void ovrfsr_fast::easu_fast_kernel<%d, 0, %d, %s>(ovrfsr::EasuArgs)" % (i, p, m) for i in (1, 2) for p in (28, 32, 40) for m in ("false", "true"))
     assert changed == want, changed
     # and the records the other fingerprint tests read carry the same values
-    for rec in ("r06_isa_fingerprint_r06.json", "r11g11b10f_isa_fingerprint.json"):
-        d = json.load(open(os.path.join(ROOT, "profiles", rec)))
+    for rec in ("r06_isa_fingerprint_r06.json", "isa_fingerprint.json"):
+        d = isa.record(rec)
         for k in added + changed:
             assert d[k] == now[k], (rec, k)

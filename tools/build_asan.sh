@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_asan.sh -- the SANITIZER build of SURVEY.md section 5 ("-fsanitize=address on host tests"): the library's host translation
-# units (postprocessor.cpp, pipeline_plan.cpp, capi.cpp, constants.cpp, nis_config.cpp, config_json.cpp and the host halves of the kernel files) compiled
+# units (postprocessor.cpp, submit_sequence.cpp, pipeline_plan.cpp, capi.cpp, constants.cpp, nis_config.cpp, config_json.cpp and the host halves of the kernel files) compiled
 # with AddressSanitizer + UndefinedBehaviorSanitizer into ab/asan.so, and the two plain-C drivers of the ABI (examples/headless.c,
 # examples/bench_node.c) likewise into ab/headless_asan / ab/bench_node_asan.  Device code is not instrumented (GPU ASan needs xnack+
 # code objects, which this pool refuses); the device side has its own checked build (fsr_bounds.h, ab/bounds.so).
@@ -36,7 +36,7 @@ done
 # (the product's kernel translation units once more with a zstd-compressed fat binary: 0.8 instead of 3.4 MB to push)
 make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA=--offload-compress BUILD=build_z build_z/fsr_kernels.o build_z/nis_kernels.o >/dev/null
 mkdir -p "$ROOT/openvr_fsr_amd/csrc/build_asan_gcc"
-for f in postprocessor pipeline_plan constants nis_config config_json capi; do
+for f in postprocessor submit_sequence pipeline_plan constants nis_config config_json capi; do
     g++ -std=c++17 -O1 -g1 -fPIC -fvisibility=hidden -D__HIP_PLATFORM_AMD__ -I"$ROCM/include" -ffp-contract=off $SAN \
         -c "$ROOT/openvr_fsr_amd/csrc/$f.cpp" -o "$ROOT/openvr_fsr_amd/csrc/build_asan_gcc/$f.o"
 done

@@ -14,7 +14,8 @@ single-thread row applies.
 One thread, C2's shape (1683x1869 -> 2244x2492), ONE EYE PER CALL through PostProcessor.apply -- the reference's call pattern -- unmasked
 (radius 2.0: two-pass) and masked (radius 0.5: mask-sorted): host time per call (400 calls, the queue drained every 8), and the wall time
 of the first apply of a fresh ctx, synchronised (plan + upload + launch: the rebuild; median of 8 fresh ctxs, the process's first one
-discarded because it loads the code objects).  Prints one line "C2 {json}".  OVRFSR_LIB selects the library, so two builds can be run
+discarded because it loads the code objects); and the masked configuration once more with cfg.pair_submit = 1, L,R per frame (host time
+per call: the submission sequencer's path, csrc/submit_sequence.cpp).  Prints one line "C2 {json}".  OVRFSR_LIB selects the library, so two builds can be run
 alternately, one process per run (profiles/pipeline_plan.txt)."""
 import os
 import sys
@@ -84,6 +85,21 @@ def c2_single_eye():
         torch.cuda.synchronize()
         res["host_us_per_call_" + name] = host / calls * 1e6
         pp.close()
+    # cfg.pair_submit = 1, masked: L,R per frame -- the first eye of a frame is only recorded, the second launches both as a batch of two
+    pp = A.PostProcessor(fsr_enabled=1, out_width=ow, out_height=oh, sharpness=0.9, radius=0.5, pair_submit=1)
+    for k in range(20):
+        pp.apply(k & 1, tex[k & 1], out=out[k & 1])
+    torch.cuda.synchronize()
+    calls, host = 400, 0.0
+    for k in range(calls):
+        t0 = time.perf_counter()
+        pp.apply(k & 1, tex[k & 1], out=out[k & 1])
+        host += time.perf_counter() - t0
+        if (k & 7) == 7:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    res["host_us_per_call_pair_submit"] = host / calls * 1e6
+    pp.close()
     print("C2 " + json.dumps(res), flush=True)
 
 
