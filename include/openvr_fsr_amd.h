@@ -74,7 +74,9 @@ typedef enum ovrfsr_format {
  * half float without its sign bit and its low mantissa bits: channel = the half float whose bits are the channel's bits shifted left by
  * 4 (R, G) or 5 (B).  That is exact for every code: denormals, +Inf (exponent 31, mantissa 0) and NaN included; the largest finite values
  * are 65024 (R, G) and 64512 (B).  Alpha reads 1.0, as D3D11 defines for a missing channel (the filters never read it).
- * The decode runs in the resolve pass in front of the pipeline, into a ctx-owned RGBA16F copy; everything behind it is the RGBA16F
+ * The decode runs where the product build's EASU, fused and outside-tile kernels stage or load their texels (a single-sample submission on
+ * a path with an upscale stage: no pass, no copy) and otherwise in the resolve pass in front of the pipeline, into a ctx-owned RGBA16F copy
+ * (multisampled submissions, the strict build, NIS, sharpen-only, tile footprints wider than 40 texels); everything behind it is the RGBA16F
  * pipeline: an R11G11B10F submission gives, byte for byte, what the RGBA16F image holding the same values (alpha 1.0) gives, on every
  * path and in every build -- same intermediate choices, same tolerances, same texel-value domain (no negative values exist; Inf and NaN
  * codes fall under the texel-value clause below: outside the parity contract, inside the memory-safety one).  Destinations: those of
@@ -84,8 +86,8 @@ typedef enum ovrfsr_format {
  * writes the format); the ctx stays enabled.  OVRFSR_FORMAT_MS(OVRFSR_FORMAT_R11G11B10F, S), S = 2, 4, 8, is accepted with the
  * multisampled layout below and the float resolve rule applied to the decoded samples (fp32 sum in sample order, times 1/S, half
  * rounded to nearest even), in the same pass.  cfg.fsr_enabled = 0 forwards the descriptor untouched.  A library older than this format
- * refuses it as OVRFSR_ERR_UNSUPPORTED: that is how a host probes for it, the ABI version is unchanged.  What the extra pass costs:
- * profiles/r11g11b10f_c5.txt. */
+ * refuses it as OVRFSR_ERR_UNSUPPORTED: that is how a host probes for it, the ABI version is unchanged.  What the pass costs where it
+ * remains, and a step without it: profiles/r11g11b10f_c5.txt, profiles/r11g11b10f_in_place.txt. */
 
 /* MULTISAMPLED INPUT (D3D11_TEXTURE2D_DESC::SampleDesc.Count > 1; the reference resolves such a texture into a single-sample copy of
  * the input's own format before filtering: PrepareResources / GetInputView, PostProcessor.cpp:196-224,520-523).  The sample count

@@ -74,7 +74,7 @@ OVRFSR_API int ovrfsr_debug_tie_audit_rcas(unsigned long long counts[5], int res
 
 #ifdef OVRFSR_BOUNDS
 // CHECKED BUILDS ONLY (-DOVRFSR_BOUNDS, fsr_bounds.h; not part of the ABI, not declared in include/openvr_fsr_amd.h, absent from the shipped
-// library): the current device's checked-accessor counters, summed over the two kernel translation units, n = ovrfsr_chk::kSlots values
+// library): the current device's checked-accessor counters, summed over the three kernel translation units, n = ovrfsr_chk::kSlots values
 // (layout: fsr_bounds.h); and the self-test launch.  tests/test_gpu_bounds.py drives them.
 OVRFSR_API int ovrfsr_debug_bounds_slots(void) { return ovrfsr_chk::kSlots; }
 OVRFSR_API int ovrfsr_debug_bounds(unsigned long long *counts, int n, int reset)
@@ -82,6 +82,7 @@ OVRFSR_API int ovrfsr_debug_bounds(unsigned long long *counts, int n, int reset)
     if (!counts || n != ovrfsr_chk::kSlots) return OVRFSR_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < n; ++i) counts[i] = 0;
     if (ovrfsr::bounds_read_fsr(counts, reset != 0) != hipSuccess) return OVRFSR_ERR_HIP;
+    if (ovrfsr::bounds_read_packed(counts, reset != 0) != hipSuccess) return OVRFSR_ERR_HIP;
     return ovrfsr::bounds_read_nis(counts, reset != 0) == hipSuccess ? OVRFSR_OK : OVRFSR_ERR_HIP;
 }
 OVRFSR_API int ovrfsr_debug_bounds_selftest(void) { return ovrfsr::bounds_selftest() == hipSuccess ? OVRFSR_OK : OVRFSR_ERR_HIP; }

@@ -211,6 +211,17 @@ template <> struct TexelBytes<ovrfsr::FMT_RGBA16F> { static constexpr int v = 8;
 template <> struct TexelBytes<ovrfsr::FMT_RGBA32F> { static constexpr int v = 16; };
 template <> struct TexelBytes<ovrfsr::FMT_RGB10A2> { static constexpr int v = 4; };
 template <> struct TexelBytes<ovrfsr::FMT_RGBA8_MS4> { static constexpr int v = 16; }; // one texel = its 4 samples
+template <> struct TexelBytes<ovrfsr::FMT_R11G11B10F> { static constexpr int v = 4; };  // one packed word (product build: decoded where it is staged / loaded)
+
+// R11G11B10F word -> fp32 (r, g, b) (header, OVRFSR_FORMAT_R11G11B10F): R bits 0-10, G 11-21, B 22-31, each the half float whose bits are the
+// channel's bits shifted left by 4 (R, G) or 5 (B) -- exact for every code, denormals, Inf and NaN included; alpha reads 1.0 (the callers'
+// constant).  These are the fp32 values a load of the resolve pass's RGBA16F copy (packed_resolve_kernel) delivers, bit for bit.
+__device__ __forceinline__ void unpack_r11g11b10f(uint32_t w, float &r, float &g, float &b)
+{
+    r = (float)__builtin_bit_cast(_Float16, (uint16_t)((w & 0x7ffu) << 4));
+    g = (float)__builtin_bit_cast(_Float16, (uint16_t)(((w >> 11) & 0x7ffu) << 4));
+    b = (float)__builtin_bit_cast(_Float16, (uint16_t)((w >> 22) << 5));
+}
 
 // The multisample resolve rule of UNORM8 channels (header, OVRFSR_FORMAT_MS): per channel (sum + S/2) >> log2 S.  R+B and G+A sum as two
 // 16-bit lanes per dword (8 x 255 + 4 fits a lane; the shift moves nothing across the mask).  resolve_kernel and the resolving staging
@@ -276,6 +287,11 @@ __device__ __forceinline__ float4 load_unit(IMG img, uint32_t pitch, int x, int 
         const uint32_t v = *OVRFSR_AT(const uint32_t, p);
         return make_float4((float)(v & 1023u) / 1023.0f, (float)((v >> 10) & 1023u) / 1023.0f, (float)((v >> 20) & 1023u) / 1023.0f,
                            (float)(v >> 30) / 3.0f);
+    } else if constexpr (FMT == ovrfsr::FMT_R11G11B10F) {
+        float4 c;
+        unpack_r11g11b10f(*OVRFSR_AT(const uint32_t, p), c.x, c.y, c.z);
+        c.w = 1.0f;
+        return c;
     } else {
         return *OVRFSR_AT(const float4, p);
     }
@@ -298,6 +314,11 @@ __device__ __forceinline__ float4 load_unit_off(IMG img, uint32_t off)
         const uint32_t v = *OVRFSR_AT(const uint32_t, p);
         return make_float4((float)(v & 1023u) / 1023.0f, (float)((v >> 10) & 1023u) / 1023.0f, (float)((v >> 20) & 1023u) / 1023.0f,
                            (float)(v >> 30) / 3.0f);
+    } else if constexpr (FMT == ovrfsr::FMT_R11G11B10F) {
+        float4 c;
+        unpack_r11g11b10f(*OVRFSR_AT(const uint32_t, p), c.x, c.y, c.z);
+        c.w = 1.0f;
+        return c;
     } else {
         return *OVRFSR_AT(const float4, p);
     }

@@ -359,6 +359,7 @@ hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const Fu
     const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
     const size_t lds = fused_lds_bytes(prec, in_fmt, mid_fmt, a.cellsW, a.cellsH);
     if (lds > kFusedLdsMax) return hipErrorInvalidValue; // never launch with less LDS than the plane layout assumes (callers pre-check: PrepareResources)
+    if (in_fmt == FMT_R11G11B10F) return strict ? hipErrorInvalidValue : launch_fused_packed(mid_fmt, out_fmt, a, grid, lds, s); // fsr_packed_kernels.hip
     OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, fused_go, mid_fmt, strict, a, grid, lds, s)
 }
 
@@ -434,6 +435,7 @@ hipError_t launch_easu_outside(int in_fmt, int mid_fmt, int out_fmt, const EasuA
         return launch_outside_staged(kTileH, in_fmt, mid_fmt, out_fmt, o, nTiles, batch, s);
     }
     const dim3 grid(nTiles, 1, batch);
+    if (in_fmt == FMT_R11G11B10F) return launch_easu_outside_packed(mid_fmt, out_fmt, a, grid, s); // fsr_packed_kernels.hip
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_outside_go, mid_fmt, a, grid, s)
 }
 
@@ -566,6 +568,11 @@ hipError_t tie_audit_read(unsigned long long out[6], bool reset)
         const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_ovrfsr_tie_audit), z, sizeof z);
     }
+    // the instances that read R11G11B10F words count in their own translation unit: sums, and the larger of the two maxima
+    unsigned long long p[6];
+    if (e == hipSuccess) e = tie_audit_read_packed(p, reset);
+    if (e == hipSuccess)
+        for (int i = 0; i < 6; ++i) out[i] = i < 4 ? out[i] + p[i] : (p[i] > out[i] ? p[i] : out[i]);
     return e;
 #else
     (void)out; (void)reset;
@@ -606,6 +613,7 @@ hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, 
         easu_fast_go<FMT_RGBA8_MS4, FMT_RGBA8, false>(easu_kernel_pitch(a.cellsW), a, grid, s);
         return hipGetLastError();
     }
+    if (in_fmt == FMT_R11G11B10F) return strict ? hipErrorInvalidValue : launch_easu_packed(out_fmt, a, grid, s); // fsr_packed_kernels.hip
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_go, strict, a, grid, lds, s)
 }
 

@@ -676,16 +676,16 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
                                                 int tile_y0, int cellsH, OVRFSR_PTR_R(COLT) col, OVRFSR_PTR_R(float) lum,
                                                 OVRFSR_PTR_R(float4) ana, uint32_t *__restrict__ tmax = nullptr)
 {
-    constexpr bool kFloatSrc = IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA32F;
+    constexpr bool kFloatSrc = IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA32F || IN_FMT == ovrfsr::FMT_R11G11B10F;
     [[maybe_unused]] float lmax = 0.0f; // this lane's largest |channel|
     static_assert(PITCH % 4 == 0, "quad sweeps need a row pitch that is a multiple of 4 cells");
     constexpr int SEGS = PITCH / 4;
     const int ncell = PITCH * cellsH;
     bool quad = false;
-    if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4)
+    if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4 || IN_FMT == ovrfsr::FMT_R11G11B10F)
         quad = tile_x0 >= 0 && tile_y0 >= 0 && tile_x0 + PITCH <= inW && tile_y0 + cellsH <= inH; // pad columns are loaded too
     if (quad) {
-        if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4) {
+        if constexpr (IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_RGBA8_MS4 || IN_FMT == ovrfsr::FMT_R11G11B10F) {
             constexpr uint32_t TB = TexelBytes<IN_FMT>::v;
             OVRFSR_PTR_R(const uint8_t) base = img + ((size_t)tile_y0 * pitchB + (size_t)tile_x0 * TB); // uniform
             // (no loop vectorisation / interleaving in these sweeps: packing across iterations costs more in register
@@ -716,6 +716,18 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
                         const float rb = (float)(v & 0xffu), gb = (float)((v >> 8) & 0xffu), bb = (float)((v >> 16) & 0xffu);
                         stc(col, idx + j, rb, gb, bb);
                         const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
+                        l[j] = b * 0.5f + (r * 0.5f + g);
+                    }
+                } else if constexpr (IN_FMT == ovrfsr::FMT_R11G11B10F) {
+                    // packed float words: one 16-byte load = 4 texels (rows are only 4-byte aligned, as RGBA8's), decoded to the fp32 values
+                    // the RGBA16F copy of the resolve pass holds -- then the RGBA16F body
+                    const u32x4_a4_t v = *OVRFSR_AT(const u32x4_a4_t, src);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        float r, g, b;
+                        unpack_r11g11b10f(v[j], r, g, b);
+                        if (tmax) lmax = fmaxf(lmax, fmaxf(fabsf(r), fmaxf(fabsf(g), fabsf(b))));
+                        stc(col, idx + j, r, g, b);
                         l[j] = b * 0.5f + (r * 0.5f + g);
                     }
                 } else {
@@ -753,6 +765,13 @@ __device__ __forceinline__ void easu_stage_fast(OVRFSR_PTR_R(const uint8_t) img,
                 const float rb = (float)(v & 0xffu), gb = (float)((v >> 8) & 0xffu), bb = (float)((v >> 16) & 0xffu);
                 stc(col, idx, rb, gb, bb);
                 const float r = unorm8_to_unit(rb), g = unorm8_to_unit(gb), b = unorm8_to_unit(bb);
+                lum[idx] = b * 0.5f + (r * 0.5f + g);
+            } else if constexpr (IN_FMT == ovrfsr::FMT_R11G11B10F) {
+                const uint32_t off = (uint32_t)sy * pitchB + (uint32_t)sx * 4u; // images span <= 4 GiB (CheckImage)
+                float r, g, b;
+                unpack_r11g11b10f(*OVRFSR_AT(const uint32_t, img + off), r, g, b);
+                if (tmax) lmax = fmaxf(lmax, fmaxf(fabsf(r), fmaxf(fabsf(g), fabsf(b))));
+                stc(col, idx, r, g, b);
                 lum[idx] = b * 0.5f + (r * 0.5f + g);
             } else {
                 const float4 c = load_unit<IN_FMT>(img, pitchB, sx, sy);
@@ -1431,7 +1450,9 @@ __device__ __forceinline__ void rcas_direct_body(const ovrfsr::RcasArgs a)
 template <int IN_FMT, int OUT_FMT>
 __global__ __launch_bounds__(256) void rcas_direct_kernel(const ovrfsr::RcasArgs a) { rcas_direct_body<IN_FMT, OUT_FMT, false>(a); }
 // exact stores: RGBA8 -> RGBA8 only (the copy / tint outside the radius is the reference's evaluation already)
+#ifndef OVRFSR_PACKED_TU /* not a template: defined once, in fsr_kernels.hip */
 __global__ __launch_bounds__(256) void rcas_direct_exact_kernel(const ovrfsr::RcasArgs a) { rcas_direct_body<ovrfsr::FMT_RGBA8, ovrfsr::FMT_RGBA8, true>(a); }
+#endif
 // ------------------------------------------------------------------------------------------------
 // RCAS, product build, unmasked RGBA8 source: neighbour reuse across lanes (north_star: "wave64 shuffles for neighbour
 // reuse").  FsrRcasF's side taps d and f (ffx_fsr1.h:698-707) are the centre taps e of the pixels to the left and right,

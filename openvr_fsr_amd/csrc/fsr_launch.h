@@ -23,6 +23,16 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
 // dst + i * h * resolve_pitch(fmt, w), rows resolve_pitch(fmt, w) bytes apart (the row bytes rounded up to 16)
 // fmt FMT_R11G11B10F (samples 1, 2, 4 or 8): 4-byte packed texels in, RGBA16F texels out -- the one source whose destination texel
 // has another size: resolve_pitch(FMT_R11G11B10F, w) is the pitch of the 8-byte copy
+// launch_easu, launch_fused and launch_easu_outside also take in_fmt FMT_R11G11B10F as it is: single-sample words decoded where the kernels
+// stage or load their texels (product build, fixed LDS pitches; hipErrorInvalidValue for the strict build and wider footprints).  Those
+// instances live in a translation unit of their own (fsr_packed_kernels.hip), so in a code object of their own: the runtime loads a code
+// object at the first launch from it, and a host that never submits the format never loads theirs -- what the other kernels' code object
+// costs to load and hold stays what it was.  The three launchers hand over to these (`a` complete, tilesXMagic included):
+hipError_t launch_easu_packed(int out_fmt, const EasuArgs &a, dim3 grid, hipStream_t s);
+hipError_t launch_fused_packed(int mid_fmt, int out_fmt, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s);
+hipError_t launch_easu_outside_packed(int mid_fmt, int out_fmt, const EasuArgs &a, dim3 grid, hipStream_t s);
+hipError_t tie_audit_read_packed(unsigned long long out[6], bool reset); // that unit's counters (-DOVRFSR_TIE_AUDIT; zeros otherwise)
+hipError_t bounds_read_packed(unsigned long long *out, bool reset);      // ... and its checked-accessor counters (-DOVRFSR_BOUNDS)
 // (resolve_pitch, easu_msaa_fused_ok -- FMT_RGBA8_MS4 resolved inside easu_fast_kernel's staging sweep -- and outside_staged_ok: fsr_sizes.h)
 hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
                           uint32_t batch, hipStream_t s);

@@ -65,7 +65,7 @@ __device__ __forceinline__ void bilinear_column4(OVRFSR_PTR_R(const uint8_t) in,
     // loaded words stay RAW across that fence: with the decode written next to the load, the scheduler hoists the first
     // shifts / converts between the load instructions and an `s_waitcnt vmcnt(1)` lands after the second load (round 3: that is
     // 2-4 loads in flight instead of 8); without the fence it sinks each pixel's loads behind the previous pixel's bounds branch.
-    constexpr bool kPairable = IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F;
+    constexpr bool kPairable = IN_FMT == ovrfsr::FMT_RGBA8 || IN_FMT == ovrfsr::FMT_RGBA16F || IN_FMT == ovrfsr::FMT_R11G11B10F;
     bool paired = false;
     if constexpr (kPairable) paired = __builtin_amdgcn_ballot_w64(bxb != bxa + 1) == 0;
     if (paired) {
@@ -99,7 +99,33 @@ __device__ __forceinline__ void bilinear_column4(OVRFSR_PTR_R(const uint8_t) in,
                        make_float4((float)pa[k][4], (float)pa[k][5], (float)pa[k][6], (float)pa[k][7]),
                        make_float4((float)pb[k][0], (float)pb[k][1], (float)pb[k][2], (float)pb[k][3]),
                        make_float4((float)pb[k][4], (float)pb[k][5], (float)pb[k][6], (float)pb[k][7]));
+        } else if constexpr (IN_FMT == ovrfsr::FMT_R11G11B10F) {
+            // packed float words: the two taps of a row are one 8-byte load, as RGBA8's; decoded behind the fence
+            typedef uint32_t u32x2_a4_t __attribute__((ext_vector_type(2), aligned(4)));
+            u32x2_a4_t pa[4], pb[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t ra = (uint32_t)clamp0(ty[k].i0, a.v.inH - 1) * a.v.in_pitch, rb = (uint32_t)clamp0(ty[k].i0 + 1, a.v.inH - 1) * a.v.in_pitch;
+                pa[k] = *OVRFSR_AT(const u32x2_a4_t, in + (ra + xoa)); pb[k] = *OVRFSR_AT(const u32x2_a4_t, in + (rb + xoa));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            auto dec = [](uint32_t v) { float4 c; unpack_r11g11b10f(v, c.x, c.y, c.z); c.w = 1.0f; return c; };
+#pragma unroll
+            for (int k = 0; k < 4; ++k) finish(k, dec(pa[k].x), dec(pa[k].y), dec(pb[k].x), dec(pb[k].y));
         }
+    } else if constexpr (IN_FMT == ovrfsr::FMT_R11G11B10F) {
+        // a lane on a clamped column: four word loads per row pair, the words kept raw across the fence like the paired form's
+        uint32_t w00[4], w10[4], w01[4], w11[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t ra = (uint32_t)clamp0(ty[k].i0, a.v.inH - 1) * a.v.in_pitch, rb = (uint32_t)clamp0(ty[k].i0 + 1, a.v.inH - 1) * a.v.in_pitch;
+            w00[k] = *OVRFSR_AT(const uint32_t, in + (ra + xoa)); w10[k] = *OVRFSR_AT(const uint32_t, in + (ra + xob));
+            w01[k] = *OVRFSR_AT(const uint32_t, in + (rb + xoa)); w11[k] = *OVRFSR_AT(const uint32_t, in + (rb + xob));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        auto dec = [](uint32_t v) { float4 c; unpack_r11g11b10f(v, c.x, c.y, c.z); c.w = 1.0f; return c; };
+#pragma unroll
+        for (int k = 0; k < 4; ++k) finish(k, dec(w00[k]), dec(w10[k]), dec(w01[k]), dec(w11[k]));
     } else {
         float4 c00[4], c10[4], c01[4], c11[4];
         // (RGBA32F texels behind a UNORM8 intermediate -- cfg.reference_formats --: two batches of 8 loads instead of one of 16; with all

@@ -14,6 +14,7 @@ inline int easu_fast_pitch(int cellsW) { return cellsW <= 32 ? 32 : cellsW <= 40
 // the EASU-only kernel also has a 28-cell pitch: exactly the footprint of a 32-pixel tile at scale 3/4
 inline int easu_kernel_pitch(int cellsW) { return cellsW <= 28 ? 28 : easu_fast_pitch(cellsW); }
 
+// (in_fmt FMT_R11G11B10F -- words decoded in staging, product build, fixed pitches only -- sizes like the RGBA16F texels it decodes to)
 inline size_t easu_lds_bytes(int prec, int in_fmt, int cellsW, int cellsH)
 {
     if (prec != PREC_FP32_STRICT && easu_fast_pitch(cellsW) != 0)

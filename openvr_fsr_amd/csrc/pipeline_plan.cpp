@@ -305,7 +305,9 @@ const char *form_name(Form f)
 // SWITCH): +inf = off, the stores of every earlier release; finite = on, the store is the strict build's bit for bit.
 float easu_tie_half_min(const Plan &plan, uint32_t inFormat, uint32_t outFormat, float halfGuard)
 {
-    const bool floatToUnorm8 = (inFormat == OVRFSR_FORMAT_RGBA16F || inFormat == OVRFSR_FORMAT_RGBA32F) && outFormat == OVRFSR_FORMAT_RGBA8_UNORM;
+    // (inFormat: what the launch reads -- R11G11B10F words decoded in staging count as the RGBA16F texels they decode to)
+    const uint32_t pf = pipeline_format(inFormat);
+    const bool floatToUnorm8 = (pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F) && outFormat == OVRFSR_FORMAT_RGBA8_UNORM;
     return floatToUnorm8 ? plan.unorm8StoreGuard : halfGuard;
 }
 
@@ -468,8 +470,50 @@ Refusal destination_refusal(const Plan &plan, uint32_t destFormat)
 // UNORM8 -- is resolved inside EASU's staging sweep (FMT_RGBA8_MS4, the same resolve_unorm8 the resolve pass runs: identical staged bytes,
 // identical output); every other multisampled input takes the resolve pass.  -DOVRFSR_MSAA_RESOLVE_PASS (measurement build, never shipped)
 // sends this path through the resolve pass too: the A/B of profiles/msaa_c2.txt.
+//
+// A single-sample R11G11B10F submission is decoded where the product build's fixed-pitch kernels stage or load their texels (easu_fast_kernel,
+// fused_kernel, easu_outside_kernel: the fp32 values the pass's RGBA16F copy would have delivered, so identical output) in every form with an
+// upscale stage; the pass and its copy remain for multisampled R11G11B10F, the strict build, NIS, sharpen-only, footprints wider than
+// 40 cells (the generic-pitch easu_kernel has no instance) and the masked launches named below.  -DOVRFSR_PACKED_RESOLVE_PASS (measurement build, never shipped) keeps the pass
+// everywhere: the A/B of profiles/r11g11b10f_in_place.txt.
+//
+// One family of masked launches keeps the pass although its kernels exist.  The bilinear fallback of the tiles outside the radius
+// (bilinear_column4) blends with contraction allowed wherever no UNORM8 rounding follows; where that blend is rounded to half -- a half
+// destination or a half intermediate -- the compiler fuses the last FMA with the rounding for some pixels of a thread and not for others, and
+// it does not choose the same pixels for texels decoded from words as for texels loaded as halves: one rounding against two, a last-bit
+// difference in about one value of 10^4.  Only the pair the default masked half pipeline launches (half intermediate AND half destination)
+// was found equal at full size (C5, 16 images); the other pairs with a half rounding and no UNORM8 one stay behind the pass until their
+// bytes are shown equal too: (half, none), (half, float), (float, half) as (destination, intermediate) of the outside-tile launch.
+static bool packed_in_staging(const Plan &plan, uint32_t destFormat)
+{
+#ifdef OVRFSR_PACKED_RESOLVE_PASS
+    (void)plan; (void)destFormat;
+    return false;
+#else
+    if (plan.inputFormat != (uint32_t)FMT_R11G11B10F || plan.useNis || plan.launchPrec != PREC_FP32 || !plan.doUpscale) return false;
+    bool fixedPitch = false, easuAlone = false;
+    switch (plan.form) {
+    case Form::UpscaleOnly: case Form::TwoPass: fixedPitch = easu_kernel_pitch(plan.cellsW) != 0; easuAlone = true; break;
+    case Form::MaskSorted: fixedPitch = easu_kernel_pitch(plan.cellsW) != 0; break;
+    case Form::Fused: case Form::FusedMaskedOutside: fixedPitch = easu_fast_pitch(plan.fusedCellsW) != 0; break;
+    default: break;
+    }
+    if (!fixedPitch) return false;
+    const bool masked = plan.tileLists || plan.maskMode[0] != MASK_ALL_INSIDE || plan.maskMode[1] != MASK_ALL_INSIDE;
+    if (masked) {
+        // what the bilinear fallback of this form stores into, and the intermediate rounding it applies on the way (none: -1)
+        const uint32_t none = ~0u, half = OVRFSR_FORMAT_RGBA16F, byte = OVRFSR_FORMAT_RGBA8_UNORM;
+        const uint32_t o = easuAlone && plan.doSharpen ? plan.intermediateFormat : destFormat, m = easuAlone ? none : plan.intermediateFormat;
+        const bool exactBlend = o == byte || m == byte, halfRounding = o == half || m == half;
+        if (!exactBlend && halfRounding && !(o == half && m == half)) return false;
+    }
+    return true;
+#endif
+}
+
 bool resolve_in_staging(const Plan &plan, uint32_t destFormat)
 {
+    if (packed_in_staging(plan, destFormat)) return true;
 #ifdef OVRFSR_MSAA_RESOLVE_PASS
     (void)plan; (void)destFormat;
     return false;

@@ -96,7 +96,8 @@ Refusal destination_refusal(const Plan &plan, uint32_t destFormat);
 // EasuArgs::tieHalfMin of one EASU launch from inFormat into outFormat.  `halfGuard`: the guard of a half store (Plan::tieHalfMin, or the
 // override an audit build puts in its place).
 float easu_tie_half_min(const Plan &plan, uint32_t inFormat, uint32_t outFormat, float halfGuard);
-// a 4-sample RGBA8 submission resolved inside EASU's staging sweep instead of the resolve pass
+// a 4-sample RGBA8 submission resolved, or a single-sample R11G11B10F one decoded, inside the kernels' staging instead of the resolve pass:
+// the pipeline then reads the submission itself (its format, pitch and stride), and no ctx-owned copy exists
 bool resolve_in_staging(const Plan &plan, uint32_t destFormat);
 
 } // namespace ovrfsr

@@ -552,8 +552,10 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
     if ((samples > 1u || base == OVRFSR_FORMAT_R11G11B10F) && !resolve_in_staging(plan_, out.format)) {
         // the reference resolves a multisampled submission into a single-sample copy of its own format (PostProcessor.cpp:196-224,520-523):
         // one resolve pass (BGRA8 re-ordered in it), then the single-sample pipeline on the copy.  An R11G11B10F submission of any sample
-        // count, 1 included, takes the same pass: it unpacks the words to an RGBA16F copy (the sampler's decode in the reference: header),
-        // 8-byte texels from 4-byte ones.
+        // count takes the same pass where the kernels cannot decode the words themselves (resolve_in_staging: multisampled, the strict build,
+        // NIS, sharpen-only, footprints wider than 40 cells): it unpacks them to an RGBA16F copy (the sampler's decode in the reference:
+        // header), 8-byte texels from 4-byte ones.  Everywhere else `in` stays the submission -- format 6, its own pitch and stride -- and
+        // the launchers take it as it is; resolved_ is never allocated.
         in.format = pipeline_format(submitted.format);
         in.pitch_bytes = resolve_pitch((int)base, in.width);
         inStride = (size_t)in.pitch_bytes * in.height;

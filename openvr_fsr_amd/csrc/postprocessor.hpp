@@ -86,7 +86,7 @@ private:
 
     // ctx-owned device buffers: upscaledTexture / sharpenedTexture, PostProcessor.h:43-45,58-59
     DeviceBuffer swizzled_;  // RGBA8 copy of a BGRA8 submission (tight pitch), see ApplyPostProcess
-    DeviceBuffer resolved_;  // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one (rows padded to 16 B), see ApplyPostProcess
+    DeviceBuffer resolved_;  // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one that is not decoded in staging (rows padded to 16 B), see ApplyPostProcess
     DeviceBuffer upscaled_;
     DeviceBuffer sharpened_;
 

@@ -34,13 +34,13 @@ done
 # uninstrumented copy ("AddressSanitizer: out of memory" at the first device allocation) -- the plain-C drivers above, which link
 # /opt/rocm's runtime directly, are fine with it.
 # (the product's kernel translation units once more with a zstd-compressed fat binary: 0.8 instead of 3.4 MB to push)
-make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA=--offload-compress BUILD=build_z build_z/fsr_kernels.o build_z/nis_kernels.o >/dev/null
+make -C "$ROOT/openvr_fsr_amd/csrc" -j8 EXTRA=--offload-compress BUILD=build_z build_z/fsr_kernels.o build_z/fsr_packed_kernels.o build_z/nis_kernels.o >/dev/null
 mkdir -p "$ROOT/openvr_fsr_amd/csrc/build_asan_gcc"
 for f in postprocessor submit_sequence pipeline_plan constants nis_config config_json capi; do
     g++ -std=c++17 -O1 -g1 -fPIC -fvisibility=hidden -D__HIP_PLATFORM_AMD__ -I"$ROCM/include" -ffp-contract=off $SAN \
         -c "$ROOT/openvr_fsr_amd/csrc/$f.cpp" -o "$ROOT/openvr_fsr_amd/csrc/build_asan_gcc/$f.o"
 done
 ${HIPCC:-$ROCM/bin/hipcc} --offload-arch=gfx950 -shared -fPIC -o "$ROOT/ab/asan_gcc.so" "$ROOT"/openvr_fsr_amd/csrc/build_asan_gcc/*.o \
-    "$ROOT/openvr_fsr_amd/csrc/build_z/fsr_kernels.o" "$ROOT/openvr_fsr_amd/csrc/build_z/nis_kernels.o"
+    "$ROOT/openvr_fsr_amd/csrc/build_z/fsr_kernels.o" "$ROOT/openvr_fsr_amd/csrc/build_z/fsr_packed_kernels.o" "$ROOT/openvr_fsr_amd/csrc/build_z/nis_kernels.o"
 python3 "$ROOT/tools/variant_fresh.py" --stamp asan "$SAN"
 echo "built ab/asan.so ab/asan_gcc.so ab/headless_asan ab/bench_node_asan ab/thread_stress_asan"
