@@ -362,6 +362,49 @@ OVRFSR_API int ovrfsr_average_gpu_time_ms(ovrfsr_ctx *ctx, float *ms, uint32_t *
  * it processes every eye inside its own Submit (VrHooks.cpp:50-62). */
 OVRFSR_API int ovrfsr_pair_pending(const ovrfsr_ctx *ctx);
 
+/* ---- hidden-area mesh: tiles the headset never shows are not processed ---------------------------
+ * A VR runtime knows, per eye, which parts of the eye image no lens ever shows: IVRSystem::GetHiddenAreaMesh(eye,
+ * k_eHiddenAreaMesh_Standard) lists them as triangles.  With a mesh set, the plan sorts the 32x32 output tiles (NVScaler: 32x24 groups)
+ * that lie ENTIRELY inside the hidden area out of its tile lists on the host, and no launch touches them.  The reference has no
+ * counterpart (its radius mask saves the expensive filter, never the pixel).  No ABI change: a host probes for these symbols.
+ *
+ * The rule, in integer arithmetic (the same on every host and in any restatement).  For an image of W x H output pixels:
+ *   vertex       u and v are clamped to [-4, 4] in double; X = (int64)floor(u*W*256 + 0.5), Y = (int64)floor(v*H*256 + 0.5).
+ *                v = 0 is the first stored row (a runtime whose v origin is at the bottom passes 1 - v).
+ *   pixel        the centre of pixel (x, y) is (256x + 128, 256y + 128).
+ *   coverage     with the three edge functions in int64: a triangle of zero area covers nothing; any other covers the pixel iff all three
+ *                are >= 0 or all three are <= 0 -- either winding, edges inclusive.
+ *   hidden       a pixel is hidden iff some triangle of its eye's mesh covers it; a tile iff every pixel of (tile & image) is hidden.
+ *   shared side-by-side textures (both eyes in one image), W2 = W / 2: the left mesh maps onto columns [0, W2), the right mesh onto
+ *                [W2, W) (X = floor(u * width of that half * 256 + 0.5) + 256 * its first column); a pixel is tested against the mesh
+ *                of its own half only.
+ * Contract:
+ *   - for every pixel outside a skipped tile the result is bit-identical to the same call with no mesh set -- in every form and format,
+ *     for batches, shared textures and pair_submit;
+ *   - pixels of skipped tiles are NOT WRITTEN: a caller-owned `out` keeps its bytes there; the ctx-owned output image is zero-filled
+ *     once, when it is allocated while a mesh is set;
+ *   - a skipped tile is always a hidden tile.  Which hidden tiles are skipped is the plan's choice per form, reported by
+ *     ovrfsr_hidden_area_stats: every hidden tile wherever the plan walks tile lists -- product arithmetic (OVRFSR_PRECISION_FP32 and
+ *     FP32_EXACT) with an upscale stage: EASU-only, two-pass, mask-sorted, fused, fused with outside tiles, NVScaler --, none in the
+ *     strict build and in the sharpen-only forms (RCAS or NVSharpen alone).  The front passes (multisample resolve, BGRA8 re-order,
+ *     R11G11B10F unpack) run on the whole image.  (In the two-kernel forms EASU still writes the INTERMEDIATE of a hidden tile that
+ *     shares an edge with a tile RCAS processes: RCAS's cross taps read it.  The destination is not written there.) */
+
+/* Set (or, with triangle_count = 0, clear; uv may then be NULL) one eye's mesh: triangles as GetHiddenAreaMesh returns them, 3 vertices x
+ * (u, v) per triangle, u, v in [0,1] of ONE eye's image; coordinates outside [0,1] are legal and clipped by the rule.  The mesh is copied.
+ * Like ovrfsr_set_config it drops a recorded pair_submit eye and makes the next apply rebuild (refused under stream capture, as any
+ * build is); ovrfsr_reset and ovrfsr_set_config keep the mesh, ovrfsr_destroy frees it.  OVRFSR_ERR_INVALID_ARGUMENT -- the stored mesh
+ * is left as it was -- for a NULL ctx, an eye other than 0 or 1, a non-finite coordinate, uv == NULL with a count, more than 4096 triangles. */
+OVRFSR_API int ovrfsr_set_hidden_area(ovrfsr_ctx *ctx, int eye, const float *uv, uint32_t triangle_count);
+/* After a successful apply: the tiles per image of that eye's list (32x32; NVScaler 32x24), and how many of them the current plan skips
+ * (0 wherever the plan ignores the mesh).  OVRFSR_ERR_INVALID_ARGUMENT before the first apply after a (re)build was asked for. */
+OVRFSR_API int ovrfsr_hidden_area_stats(const ovrfsr_ctx *ctx, int eye, uint32_t *tiles_total, uint32_t *tiles_skipped);
+/* Constants-only, no GPU: the classification rule itself, for known-answer tests and for a host that wants a preview.  One eye's mesh on
+ * an out_w x out_h image (1..16384 each) cut into tile_w x tile_h tiles: hidden[tileY * ceil(out_w / tile_w) + tileX] = 1 for a hidden
+ * tile, else 0.  hidden_len: bytes at `hidden`; too few (or any bad argument, checked as above): OVRFSR_ERR_INVALID_ARGUMENT, nothing written. */
+OVRFSR_API int ovrfsr_hidden_tiles(const float *uv, uint32_t triangle_count, uint32_t out_w, uint32_t out_h,
+                                   uint32_t tile_w, uint32_t tile_h, uint8_t *hidden, size_t hidden_len);
+
 /* ---- constants-only entry points (known-answer tests; no GPU needed) ------------------------- */
 
 /* FsrEasuCon (src/fsr/ffx_fsr1.h:156-202); con = con0|con1|con2|con3 */

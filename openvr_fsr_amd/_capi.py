@@ -116,6 +116,10 @@ def library():
     L.ovrfsr_save_ppm.argtypes = [C.POINTER(Image), C.c_char_p, C.c_void_p]
     L.ovrfsr_save_dds.argtypes = [C.POINTER(Image), C.c_char_p, C.c_void_p]
     L.ovrfsr_pair_pending.argtypes = [C.c_void_p]
+    if hasattr(L, "ovrfsr_set_hidden_area"):  # probed by symbol, as a host does: an older build of ABI 5 under OVRFSR_LIB (A/B runs) has none
+        L.ovrfsr_set_hidden_area.argtypes = [C.c_void_p, C.c_int, f32p, C.c_uint32]
+        L.ovrfsr_hidden_area_stats.argtypes = [C.c_void_p, C.c_int, u32p, u32p]
+        L.ovrfsr_hidden_tiles.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t]
     if L.ovrfsr_abi_version() != 5:
         raise OvrFsrError(1, "ABI version mismatch")
     _LIB = L
@@ -164,6 +168,24 @@ def nis_coefs():
     s = np.ctypeslib.as_array(L.ovrfsr_nis_coef_scale(), shape=(64, 8)).copy()
     u = np.ctypeslib.as_array(L.ovrfsr_nis_coef_usm(), shape=(64, 8)).copy()
     return s, u
+
+
+def mesh_array(uv):
+    """triangles as ovrfsr_set_hidden_area takes them: anything that reshapes to [n, 3, 2] (u, v) -> (contiguous float32 array, n)"""
+    m = np.ascontiguousarray(np.asarray(uv if uv is not None else [], np.float32).reshape(-1, 3, 2))
+    return m, m.shape[0]
+
+
+def hidden_tiles(uv, outW, outH, tileW=32, tileH=32):
+    """ovrfsr_hidden_tiles: the [tilesY, tilesX] uint8 map of the tiles one eye's mesh hides entirely (no GPU)."""
+    m, n = mesh_array(uv)
+    tx, ty = (outW + tileW - 1) // tileW, (outH + tileH - 1) // tileH
+    hidden = np.zeros((ty, tx), np.uint8)
+    rc = library().ovrfsr_hidden_tiles(m.ctypes.data_as(C.POINTER(C.c_float)) if n else None, n, outW, outH, tileW, tileH,
+                                       hidden.ctypes.data_as(C.POINTER(C.c_uint8)), hidden.size)
+    if rc != 0:
+        raise OvrFsrError(rc)
+    return hidden
 
 
 def config_from_json(text):

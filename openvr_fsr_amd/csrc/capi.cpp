@@ -92,6 +92,44 @@ OVRFSR_API void ovrfsr_debug_fail_resource(int nth) { ovrfsr::debug_fail_resourc
 
 OVRFSR_API int ovrfsr_pair_pending(const ovrfsr_ctx *ctx) { return ctx && ctx->pp && ctx->pp->PairPending() ? 1 : 0; }
 
+// ---- hidden-area mesh (header).  The argument checks live here: the planner's refusal table knows nothing of meshes.
+namespace {
+constexpr uint32_t kMaxHiddenTriangles = 4096;
+bool mesh_ok(const float *uv, uint32_t triangle_count)
+{
+    if (triangle_count > kMaxHiddenTriangles || (!uv && triangle_count)) return false;
+    for (size_t i = 0; i < 6 * (size_t)triangle_count; ++i)
+        if (!std::isfinite(uv[i])) return false;
+    return true;
+}
+} // namespace
+
+OVRFSR_API int ovrfsr_set_hidden_area(ovrfsr_ctx *ctx, int eye, const float *uv, uint32_t triangle_count)
+{
+    if (!ctx || (eye != OVRFSR_EYE_LEFT && eye != OVRFSR_EYE_RIGHT) || !mesh_ok(uv, triangle_count)) return OVRFSR_ERR_INVALID_ARGUMENT; // the stored mesh stays
+    return guarded([&] { return ctx->pp->SetHiddenArea(eye, uv, triangle_count); });
+}
+
+OVRFSR_API int ovrfsr_hidden_area_stats(const ovrfsr_ctx *ctx, int eye, uint32_t *tiles_total, uint32_t *tiles_skipped)
+{
+    if (!ctx || (eye != OVRFSR_EYE_LEFT && eye != OVRFSR_EYE_RIGHT) || !tiles_total || !tiles_skipped) return OVRFSR_ERR_INVALID_ARGUMENT;
+    return guarded([&] { return ctx->pp->HiddenAreaStats(eye, tiles_total, tiles_skipped); });
+}
+
+OVRFSR_API int ovrfsr_hidden_tiles(const float *uv, uint32_t triangle_count, uint32_t out_w, uint32_t out_h, uint32_t tile_w, uint32_t tile_h,
+                                   uint8_t *hidden, size_t hidden_len)
+{
+    if (!mesh_ok(uv, triangle_count) || !hidden || out_w == 0 || out_h == 0 || out_w > 16384 || out_h > 16384 || tile_w == 0 || tile_h == 0 ||
+        tile_w > 16384 || tile_h > 16384)
+        return OVRFSR_ERR_INVALID_ARGUMENT;
+    const size_t tiles = (size_t)((out_w + tile_w - 1) / tile_w) * ((out_h + tile_h - 1) / tile_h);
+    if (hidden_len < tiles) return OVRFSR_ERR_INVALID_ARGUMENT; // (nothing written)
+    return guarded([&] {
+        ovrfsr::hidden_tiles(uv, triangle_count, nullptr, 0, false, out_w, out_h, tile_w, tile_h, hidden);
+        return (int)OVRFSR_OK;
+    });
+}
+
 OVRFSR_API void ovrfsr_config_default(ovrfsr_config *cfg)
 {
     if (!cfg) return;

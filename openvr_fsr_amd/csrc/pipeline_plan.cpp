@@ -178,20 +178,121 @@ inline uint32_t xcd_source(uint32_t b, uint32_t n)
     return b < full ? (b & 7u) * (full >> 3) + (b >> 3) : b;
 }
 
+// ---- the hidden-area rule (header, ovrfsr_hidden_tiles) ------------------------------------------------------------------------------
+// One triangle in 1/256-pixel fixed point, with the pixels whose centres its bounding box holds (clipped to its mesh's columns and the image)
+struct HiddenTri {
+    int64_t x[3], y[3];
+    int64_t px0, px1, py0, py1; // inclusive pixel ranges; empty where px0 > px1 or py0 > py1
+};
+
+// u, v -> fixed point: clamped to [-4, 4] in double, then floor(u * n * 256 + 0.5)
+inline int64_t hidden_fixed(float c, uint32_t n)
+{
+    const double d = std::min(4.0, std::max(-4.0, (double)c));
+    return (int64_t)std::floor(d * (double)n * 256.0 + 0.5);
+}
+inline int64_t floor_div256(int64_t a) { return a >= 0 ? a / 256 : -((-a + 255) / 256); }
+
+// the triangles of one mesh that can cover a pixel of columns [x0, x1): zero-area ones and empty boxes are dropped here
+void hidden_triangles(const float *uv, uint32_t n, uint32_t x0, uint32_t x1, uint32_t outH, std::vector<HiddenTri> &tris)
+{
+    if (!uv || x1 <= x0) return;
+    for (uint32_t i = 0; i < n; ++i) {
+        HiddenTri t;
+        for (int k = 0; k < 3; ++k) {
+            t.x[k] = hidden_fixed(uv[6 * i + 2 * k], x1 - x0) + 256 * (int64_t)x0;
+            t.y[k] = hidden_fixed(uv[6 * i + 2 * k + 1], outH);
+        }
+        const int64_t area = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.y[1] - t.y[0]) * (t.x[2] - t.x[0]);
+        if (area == 0) continue; // covers nothing
+        const int64_t xa = std::min({t.x[0], t.x[1], t.x[2]}), xb = std::max({t.x[0], t.x[1], t.x[2]});
+        const int64_t ya = std::min({t.y[0], t.y[1], t.y[2]}), yb = std::max({t.y[0], t.y[1], t.y[2]});
+        // pixel centres 256 p + 128 inside [a, b]: p >= ceil((a - 128) / 256), p <= floor((b - 128) / 256)
+        t.px0 = std::max<int64_t>(floor_div256(xa - 128 + 255), x0); t.px1 = std::min<int64_t>(floor_div256(xb - 128), (int64_t)x1 - 1);
+        t.py0 = std::max<int64_t>(floor_div256(ya - 128 + 255), 0); t.py1 = std::min<int64_t>(floor_div256(yb - 128), (int64_t)outH - 1);
+        if (t.px0 <= t.px1 && t.py0 <= t.py1) tris.push_back(t);
+    }
+}
+
+} // namespace
+
+void hidden_tiles(const float *left, uint32_t leftTriangles, const float *right, uint32_t rightTriangles, bool shared, uint32_t outW, uint32_t outH,
+                  uint32_t tileW, uint32_t tileH, uint8_t *hidden)
+{
+    const uint32_t tx = (outW + tileW - 1) / tileW, ty = (outH + tileH - 1) / tileH;
+    std::fill(hidden, hidden + (size_t)tx * ty, (uint8_t)0);
+    std::vector<HiddenTri> tris;
+    if (shared) {
+        hidden_triangles(left, leftTriangles, 0, outW / 2, outH, tris);
+        hidden_triangles(right, rightTriangles, outW / 2, outW, outH, tris);
+    } else {
+        hidden_triangles(left, leftTriangles, 0, outW, outH, tris);
+    }
+    if (tris.empty()) return;
+    // one band of tile rows at a time: a byte per pixel of the band, every triangle rasterised over (its box & the band) with the three
+    // edge functions stepped along the row -- the work follows the boxes' area, the memory one band
+    std::vector<uint8_t> cover;
+    for (uint32_t band = 0; band < ty; ++band) {
+        const int64_t y0 = (int64_t)band * tileH, y1 = std::min<int64_t>(y0 + tileH, outH) - 1;
+        bool touched = false;
+        for (const HiddenTri &t : tris) {
+            const int64_t ya = std::max(t.py0, y0), yb = std::min(t.py1, y1);
+            if (ya > yb) continue;
+            if (!touched) { cover.assign((size_t)outW * (size_t)(y1 - y0 + 1), 0); touched = true; }
+            for (int64_t y = ya; y <= yb; ++y) {
+                uint8_t *row = cover.data() + (size_t)(y - y0) * outW;
+                const int64_t cx = 256 * t.px0 + 128, cy = 256 * y + 128;
+                int64_t e[3], step[3];
+                for (int k = 0; k < 3; ++k) {
+                    const int k1 = (k + 1) % 3;
+                    const int64_t dx = t.x[k1] - t.x[k], dy = t.y[k1] - t.y[k];
+                    e[k] = dx * (cy - t.y[k]) - dy * (cx - t.x[k]);
+                    step[k] = -256 * dy;
+                }
+                for (int64_t x = t.px0; x <= t.px1; ++x) {
+                    // either winding, edges inclusive
+                    if ((e[0] >= 0 && e[1] >= 0 && e[2] >= 0) || (e[0] <= 0 && e[1] <= 0 && e[2] <= 0)) row[x] = 1;
+                    e[0] += step[0]; e[1] += step[1]; e[2] += step[2];
+                }
+            }
+        }
+        if (!touched) continue;
+        const uint32_t rows = (uint32_t)(y1 - y0 + 1);
+        for (uint32_t txi = 0; txi < tx; ++txi) {
+            const uint32_t xa = txi * tileW, xb = std::min(xa + tileW, outW);
+            bool all = true;
+            for (uint32_t r = 0; r < rows && all; ++r) {
+                const uint8_t *row = cover.data() + (size_t)r * outW;
+                for (uint32_t x = xa; x < xb && all; ++x) all = row[x] != 0;
+            }
+            hidden[(size_t)band * tx + txi] = all ? 1 : 0;
+        }
+    }
+}
+
+namespace {
+
 // The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one mask group
 // inside the radius (EASU kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel).
-void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH)
+// `hidden` (a hidden-area mesh is set; null: none): per eye, the tiles no lens shows.  They are in neither list.  `classify` = false (no
+// mixed mask: the lists exist for the mesh alone): every other tile is an "inside" tile, whatever the radius -- the kernel that runs on it
+// is the one the launch without lists runs, mask test included.  In the two-kernel forms (`rcasForm`: Form::MaskSorted, Form::TwoPass) a
+// hidden tile 4-adjacent to a tile RCAS processes joins the ring, so that EASU still writes the intermediate texels RCAS's cross taps read.
+void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH, const std::vector<uint8_t> *hidden = nullptr,
+                bool classify = true, Form rcasForm = Form::None)
 {
     const uint32_t outW = p.outputWidth, outH = p.outputHeight;
     const uint32_t tx = (outW + tileW - 1) / tileW, ty = (outH + tileH - 1) / tileH;
     const uint32_t gpx = tileW / groupW, gpy = tileH / groupH; // mask groups per tile
     std::vector<uint32_t> &lists = p.lists, &spans = p.spans;
-    std::vector<uint32_t> in[2], outl[2];
+    std::vector<uint32_t> in[2], outl[2], rcas[2];
+    p.nTiles = tx * ty;
     for (int eye = 0; eye < 2; ++eye) {
         const uint32_t *c = p.centre[eye];
         for (uint32_t t = 0; t < tx * ty; ++t) {
+            if (hidden && hidden[eye][t]) { ++p.nSkipped[eye]; continue; }
             const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            bool any = false;
+            bool any = !classify;
             for (uint32_t g = 0; g < gpx * gpy && !any; ++g) {
                 const uint32_t gx = gpx * txi + (g % gpx), gy = gpy * tyi + (g / gpx);
                 const uint32_t cx = gx * groupW + groupW / 2, cy = gy * groupH + groupH / 2;
@@ -201,27 +302,49 @@ void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32
             (any ? in[eye] : outl[eye]).push_back(t);
         }
     }
+    // what RCAS walks, in raster order: the inside tiles -- in the two-pass form under a mesh, every tile that is not hidden
+    const bool rcasOwnList = hidden && rcasForm == Form::TwoPass;
+    for (int eye = 0; eye < 2; ++eye) {
+        rcas[eye] = in[eye];
+        if (rcasOwnList) {
+            rcas[eye].insert(rcas[eye].end(), outl[eye].begin(), outl[eye].end());
+            std::sort(rcas[eye].begin(), rcas[eye].end());
+        }
+    }
     std::vector<uint32_t> ring[2];
     for (int eye = 0; eye < 2; ++eye) {
         std::vector<uint8_t> isIn((size_t)tx * ty, 0);
-        for (uint32_t t : in[eye]) isIn[t] = 1;
-        for (uint32_t t : outl[eye]) {
+        auto adjacent = [&](uint32_t t) {
             const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            const bool adj = (txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx]);
-            if (adj) ring[eye].push_back(t);
+            return (txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx]);
+        };
+        if (rcasOwnList) { // (the outside tiles' intermediate is the outside-tile launch's: the ring holds hidden tiles only)
+            for (uint32_t t : rcas[eye]) isIn[t] = 1;
+            for (uint32_t t = 0; t < tx * ty; ++t)
+                if (hidden[eye][t] && adjacent(t)) ring[eye].push_back(t);
+            continue;
         }
+        for (uint32_t t : in[eye]) isIn[t] = 1;
+        for (uint32_t t : outl[eye])
+            if (adjacent(t)) ring[eye].push_back(t);
+        if (hidden && rcasForm == Form::MaskSorted) {
+            for (uint32_t t = 0; t < tx * ty; ++t)
+                if (hidden[eye][t] && adjacent(t)) ring[eye].push_back(t);
+        } // (a hidden ring tile is still a skipped one: nothing of the destination is written there)
     }
     p.listsShared = in[0] == in[1];
+    if (hidden) p.listsShared = p.listsShared && outl[0] == outl[1] && ring[0] == ring[1]; // (the final lists: without a mesh they follow from in[])
     // RCAS on the mask-sorted form (RGBA8): per 32-row band, runs of adjacent tiles touching the radius, cut into the DPP
     // kernel's 62-column segments (rcas_dpp_kernel<.., true>): {x0 | tileY << 16, xEnd}
     if (tileW == (uint32_t)kTileW && tileH == (uint32_t)kRcasDppTileH && outW < 65536u && ty < 65536u) {
         for (int eye = 0; eye < 2; ++eye) {
+            const std::vector<uint32_t> &run = rcas[eye]; // row-major here
             p.spanOff[eye] = spans.size() / 2;
-            for (size_t i = 0; i < in[eye].size();) { // in[] is row-major here
+            for (size_t i = 0; i < run.size();) {
                 size_t j = i;
-                while (j + 1 < in[eye].size() && in[eye][j + 1] == in[eye][j] + 1 && (in[eye][j + 1] / tx) == (in[eye][i] / tx)) ++j;
-                const uint32_t tyi = in[eye][i] / tx, xa = (in[eye][i] - tyi * tx) * tileW;
-                const uint32_t xb = std::min((in[eye][j] - tyi * tx + 1) * tileW, outW);
+                while (j + 1 < run.size() && run[j + 1] == run[j] + 1 && (run[j + 1] / tx) == (run[i] / tx)) ++j;
+                const uint32_t tyi = run[i] / tx, xa = (run[i] - tyi * tx) * tileW;
+                const uint32_t xb = std::min((run[j] - tyi * tx + 1) * tileW, outW);
                 for (uint32_t x0 = xa; x0 < xb; x0 += kRcasDppTileW) {
                     spans.push_back(x0 | (tyi << 16));
                     spans.push_back(std::min(x0 + (uint32_t)kRcasDppTileW, xb));
@@ -255,6 +378,13 @@ void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32
         p.nRing[eye] = (uint32_t)ring[eye].size();
         p.listOffRing[eye] = lists.size(); lists.insert(lists.end(), ring[eye].begin(), ring[eye].end());
         p.listOffOutside[eye] = lists.size(); lists.insert(lists.end(), outl[eye].begin(), outl[eye].end());
+        // RCAS: the inside list, or (two-pass under a mesh) a fourth segment of its own
+        p.nRcas[eye] = p.nInside[eye]; p.listOffRcas[eye] = p.listOffInside[eye];
+        if (rcasOwnList) {
+            xcd_order(rcas[eye]);
+            p.nRcas[eye] = (uint32_t)rcas[eye].size();
+            p.listOffRcas[eye] = lists.size(); lists.insert(lists.end(), rcas[eye].begin(), rcas[eye].end());
+        }
     }
     // One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin
     // (first column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of
@@ -332,7 +462,8 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
     return OVRFSR_OK;
 }
 
-Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan)
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
+                      const HiddenArea *hidden)
 {
     Plan p;
     p.inputWidth = width; p.inputHeight = height; p.inputFormat = format;
@@ -391,12 +522,11 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     }
     reciprocals(p);
     if (p.doUpscale) tap_tables(p);
-    p.tileLists = p.doUpscale && p.launchPrec == PREC_FP32 && (p.maskMode[0] == MASK_MIXED || p.maskMode[1] == MASK_MIXED);
-    if (p.tileLists) {
-        // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
-        if (cfg.use_nis) tile_lists(p, 32, 24, 32, 24);
-        else tile_lists(p, kTileW, kTileH, 16, 16);
-    }
+    p.maskLists = p.doUpscale && p.launchPrec == PREC_FP32 && (p.maskMode[0] == MASK_MIXED || p.maskMode[1] == MASK_MIXED);
+    // a hidden-area mesh (header, ovrfsr_set_hidden_area): product arithmetic and an upscale stage, like the lists it is built on.  The lists
+    // then exist whatever the mask; the FORM below is chosen from the mask alone -- an unmasked two-pass stays two-pass, launched over lists
+    p.hiddenArea = hidden && (hidden->triangles[0] || hidden->triangles[1]) && p.doUpscale && p.launchPrec == PREC_FP32;
+    p.tileLists = p.maskLists || p.hiddenArea;
     if (p.doSharpen && !cfg.use_nis) {
         float s = cfg.sharpness;
         s = s < 1.0f ? s : 1.0f; // AClampF1(x,0,1) = max(0,min(x,1)), PostProcessor.cpp:420
@@ -420,14 +550,14 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     if (cfg.reference_formats && floatIn && cfg.fused == 1) return kRefusals[R_FUSED_FLOAT_REFERENCE];
     const bool byteMidOfFloat = floatIn && mid == OVRFSR_FORMAT_RGBA8_UNORM;
     const bool fusedFits = fused_lds_bytes(p.launchPrec, (int)pf, (int)mid, p.fusedCellsW, p.fusedCellsH) <= kFusedLdsMax;
-    const bool autoFused = !tenBit && !byteMidOfFloat && cfg.fused == -1 && p.tileLists && p.fusedCellsW <= 40 && fusedFits;
+    const bool autoFused = !tenBit && !byteMidOfFloat && cfg.fused == -1 && p.maskLists && p.fusedCellsW <= 40 && fusedFits;
     // auto on a masked product-build EASU+RCAS pipeline: the two-pass kernels on the tiles touching the radius, tiles
     // outside written in final form (ApplySorted); cfg.fused = 1 keeps the single fused kernel on those tiles
     // Measured: with 4-byte pixels the sorted two-pass form wins (C2 shape, radius 0.5: +13 %); with 8/16-byte
     // pixels the outside kernel dominates the frame, and the three dependent launches of the sorted form lose to the
     // fused kernel (C5: -15 %), so those keep it.  The condition is the INTERMEDIATE's format: under cfg.reference_formats a float source
     // has a UNORM8 intermediate too, and takes this form (RCAS on rcas_dpp_kernel's span records; profiles/reference_formats.txt).
-    const bool sorted = cfg.fused == -1 && p.tileLists && both && !cfg.use_nis && (pf == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) &&
+    const bool sorted = cfg.fused == -1 && p.maskLists && both && !cfg.use_nis && (pf == OVRFSR_FORMAT_RGBA8_UNORM || floatIn) &&
                         mid == OVRFSR_FORMAT_RGBA8_UNORM;
     bool fused = false;
     if ((cfg.fused == 1 || (autoFused && !sorted)) && both && !cfg.use_nis) {
@@ -436,7 +566,7 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
         fused = true;
     }
     if (fused && exact) return kRefusals[R_EXACT_FUSED]; // (fused = -1 picks it for half / float intermediates only, refused above)
-    p.form = sorted ? Form::MaskSorted : fused ? (p.tileLists ? Form::FusedMaskedOutside : Form::Fused)
+    p.form = sorted ? Form::MaskSorted : fused ? (p.maskLists ? Form::FusedMaskedOutside : Form::Fused)
            : both ? Form::TwoPass : p.doUpscale ? Form::UpscaleOnly : p.doSharpen ? Form::SharpenOnly : Form::None;
 
     // The tiles outside the radius of a masked pass are independent of the tiles touching it: their kernel can run on the ctx's auxiliary
@@ -446,7 +576,26 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     // RGBA8 one does -- its three launches are short, and the fork / join pair costs ~10 us per cross-queue wait
     BatchView v{};
     v.inW = (int32_t)width; v.inH = (int32_t)height; v.outW = (int32_t)ow; v.outH = (int32_t)oh;
-    p.overlapOutside = p.tileLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
+    p.overlapOutside = p.maskLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
+
+    if (p.tileLists) {
+        // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
+        const uint32_t tileW = 32, tileH = cfg.use_nis ? 24 : (uint32_t)kTileH;
+        if (!p.hiddenArea) {
+            tile_lists(p, tileW, tileH, cfg.use_nis ? 32 : 16, cfg.use_nis ? 24 : 16);
+        } else {
+            // one eye per texture: each eye's own mesh; a shared side-by-side texture: one map of both halves, the same for both "eyes"
+            const uint32_t tiles = ((ow + tileW - 1) / tileW) * ((oh + tileH - 1) / tileH);
+            std::vector<uint8_t> map[2];
+            for (int eye = 0; eye < 2; ++eye) {
+                map[eye].resize(tiles);
+                if (onlyOneEye) hidden_tiles(hidden->uv[eye], hidden->triangles[eye], nullptr, 0, false, ow, oh, tileW, tileH, map[eye].data());
+                else if (eye == 0) hidden_tiles(hidden->uv[0], hidden->triangles[0], hidden->uv[1], hidden->triangles[1], true, ow, oh, tileW, tileH, map[0].data());
+                else map[1] = map[0];
+            }
+            tile_lists(p, tileW, tileH, cfg.use_nis ? 32 : 16, cfg.use_nis ? 24 : 16, map, p.maskLists, p.form);
+        }
+    }
     *plan = std::move(p);
     return Refusal{};
 }
@@ -499,7 +648,8 @@ static bool packed_in_staging(const Plan &plan, uint32_t destFormat)
     default: break;
     }
     if (!fixedPitch) return false;
-    const bool masked = plan.tileLists || plan.maskMode[0] != MASK_ALL_INSIDE || plan.maskMode[1] != MASK_ALL_INSIDE;
+    // (maskLists, not tileLists: a hidden-area mesh must not move the decision -- the pixels it leaves are the bytes of the call without it)
+    const bool masked = plan.maskLists || plan.maskMode[0] != MASK_ALL_INSIDE || plan.maskMode[1] != MASK_ALL_INSIDE;
     if (masked) {
         // what the bilinear fallback of this form stores into, and the intermediate rounding it applies on the way (none: -1)
         const uint32_t none = ~0u, half = OVRFSR_FORMAT_RGBA16F, byte = OVRFSR_FORMAT_RGBA8_UNORM;

@@ -51,7 +51,11 @@ struct Plan {
     bool doUpscale = false, doSharpen = false;
     bool useNis = false;         // NVScaler / NVSharpen in place of EASU / RCAS
     Form form = Form::None;
-    bool tileLists = false;      // masked launches walk the per-eye tile lists below (product arithmetic, an upscale stage, a mixed mask)
+    bool tileLists = false;      // the launches walk the per-eye tile lists below: product arithmetic, an upscale stage, and a mixed mask
+                                 // (maskLists) or a hidden-area mesh (hiddenArea)
+    bool maskLists = false;      // ... because of the mask: what tileLists is without a mesh.  The form is chosen from this one alone
+    bool hiddenArea = false;     // a hidden-area mesh is in effect (HiddenArea): hidden tiles are in no list but the ring; the strict build,
+                                 // sharpen-only forms and anything without an upscale stage ignore the mesh
     bool overlapOutside = false; // ... and their outside-tile kernel runs on the ctx's auxiliary stream (see PostProcessor::Fork)
     // pipeline: what the kernels see in the submission's place; intermediate: the upscale stage's destination in front of a sharpen stage;
     // owned: the textures the ctx creates for itself (cfg.reference_formats)
@@ -83,13 +87,32 @@ struct Plan {
     uint32_t nInside[2] = {0, 0}, nOutside[2] = {0, 0}, nRing[2] = {0, 0}, nSpans[2] = {0, 0};
     size_t listOffInside[2] = {0, 0}, listOffOutside[2] = {0, 0}, listOffRing[2] = {0, 0}, spanOff[2] = {0, 0}; // spanOff in segments
     bool listsShared = false;    // both eyes have identical lists
+    // hiddenArea: tiles per image, and how many of them no launch touches (hidden tiles; a skipped tile is always a hidden one).  In the
+    // two-kernel forms a hidden tile 4-adjacent to a tile RCAS processes stays in the ring segment -- EASU writes the intermediate texels
+    // RCAS's cross taps read -- and has no outside entry and no span.  Two-pass: RCAS walks a list of its own (every tile that is not
+    // hidden, inside | outside merged in raster order), and the spans are cut from that list
+    uint32_t nTiles = 0, nSkipped[2] = {0, 0}, nRcas[2] = {0, 0};
+    size_t listOffRcas[2] = {0, 0};
 };
+
+// ovrfsr_set_hidden_area's meshes as the planner takes them: per eye, `triangles` triangles of 3 x (u, v) floats (header: the rule)
+struct HiddenArea {
+    const float *uv[2] = {nullptr, nullptr};
+    uint32_t triangles[2] = {0, 0};
+};
+// The classification rule (header, ovrfsr_hidden_tiles): hidden[tileY * tilesX + tileX] = 1 where every pixel of (tile & image) is covered by
+// some triangle.  Integer arithmetic throughout; cost follows the triangles' bounding boxes.  With `right` (a shared side-by-side texture)
+// `left` maps onto columns [0, outW / 2) and `right` onto [outW / 2, outW), each pixel tested against the mesh of its own half only.
+void hidden_tiles(const float *left, uint32_t leftTriangles, const float *right, uint32_t rightTriangles, bool shared, uint32_t outW, uint32_t outH,
+                  uint32_t tileW, uint32_t tileH, uint8_t *hidden);
 
 // ovrfsr_output_size behind its argument checks
 int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint32_t *outW, uint32_t *outH);
 
 // `format`: canonical (a single-sample encoding reduced to its base format).  On a refusal *plan is left as it was.
-Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan);
+// `hidden`: the ctx's hidden-area meshes, or null (none set): the plan is then what it has always been.
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
+                      const HiddenArea *hidden = nullptr);
 
 // what depends on the destination the call names
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat);

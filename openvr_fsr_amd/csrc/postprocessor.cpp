@@ -174,6 +174,26 @@ int PostProcessor::SetConfig(const ovrfsr_config &cfg)
     return OVRFSR_OK;
 }
 
+// ovrfsr_set_hidden_area behind its argument checks (capi.cpp): keep a copy of the mesh, then what SetConfig does -- a recorded pair_submit
+// eye is dropped and the next apply plans afresh (refused under stream capture, as any build is).  Reset keeps the mesh.
+int PostProcessor::SetHiddenArea(int eye, const float *uv, uint32_t triangles)
+{
+    std::vector<float> copy(uv, uv + (uv ? 6 * (size_t)triangles : 0)); // (may throw: the stored mesh is then still the old one)
+    hiddenUv_[eye & 1].swap(copy);
+    Reset();
+    return OVRFSR_OK;
+}
+
+int PostProcessor::HiddenAreaStats(int eye, uint32_t *tilesTotal, uint32_t *tilesSkipped)
+{
+    if (!initialized_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "no plan yet: hidden-area statistics follow a successful apply");
+    // tiles per image as the plan's lists count them: 32x32, NVScaler 32x24
+    const uint32_t th = plan_.useNis && plan_.doUpscale ? 24u : (uint32_t)kTileH;
+    *tilesTotal = ((plan_.outputWidth + kTileW - 1) / kTileW) * ((plan_.outputHeight + th - 1) / th);
+    *tilesSkipped = plan_.hiddenArea ? plan_.nSkipped[eye & 1] : 0u;
+    return OVRFSR_OK;
+}
+
 int PostProcessor::CheckImage(const ovrfsr_image *img, const char *name, bool input)
 {
     if (!img || !img->data) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, std::string(name) + ": null image");
@@ -233,7 +253,9 @@ int PostProcessor::IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midS
 // configuration allocates nothing.  What the plan holds is then created on the device, in a fixed order (fault injection counts creations).
 int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneEye)
 {
-    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_);
+    HiddenArea hidden;
+    for (int eye = 0; eye < 2; ++eye) { hidden.uv[eye] = hiddenUv_[eye].data(); hidden.triangles[eye] = (uint32_t)(hiddenUv_[eye].size() / 6); }
+    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden);
     if (refused) return Fail(refused.status, refused.text);
     if (plan_.useNis) { // coef_scale[512] | coef_usm[512], PostProcessor.cpp:366-382
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
@@ -364,7 +386,7 @@ hipError_t PostProcessor::InsideThenOutside(const EyePass &ps, In inside, Out ou
 {
     ps.Select(inside); ps.Select(outside);
     hipError_t e = hipSuccess;
-    if (plan_.nInside[ps.eye]) {
+    if (plan_.nInside[ps.eye] + ring) { // (an empty list is no launch: under a hidden-area mesh any of the lists can be empty)
         inside.tileList = InsideList(ps.eye);
         e = launchInside(inside, plan_.nInside[ps.eye] + ring);
     }
@@ -396,8 +418,11 @@ int PostProcessor::ApplyUpscaling(uint32_t n, int firstEye, int alternate, const
     EasuArgs a;
     FillEasu(a, in, inStride, out, outStride, firstEye, alternate);
     if (!plan_.tileLists) return Launched(launch_easu(plan_.launchPrec, (int)in.format, (int)out.format, a, n, stream), "EASU");
+    // two-pass under a hidden-area mesh: the hidden tiles next to a tile RCAS processes follow the inside list (Plan::nRing), so that this
+    // launch writes the intermediate texels RCAS's cross taps read there
+    const bool hiddenRing = plan_.hiddenArea && plan_.form == Form::TwoPass;
     return ForEachEyePass(n, firstEye, alternate, stream, "EASU", [&](const EyePass &ps, hipStream_t aux) {
-        return InsideThenOutside(ps, a, a, 0,
+        return InsideThenOutside(ps, a, a, hiddenRing ? plan_.nRing[ps.eye] : 0,
             [&](const EasuArgs &b, uint32_t tiles) { return launch_easu(plan_.launchPrec, (int)in.format, (int)out.format, b, ps.cnt, stream, tiles); },
             [&](const EasuArgs &b, uint32_t tiles) { return launch_easu_outside((int)in.format, -1, (int)out.format, b, tiles, ps.cnt, aux); });
     });
@@ -530,6 +555,23 @@ int PostProcessor::ApplySharpening(uint32_t n, int firstEye, int alternate, cons
     }
     RcasArgs a;
     FillRcas(a, in, inStride, out, outStride, firstEye, alternate);
+    if (plan_.hiddenArea && plan_.form == Form::TwoPass) {
+        // under a hidden-area mesh RCAS walks the plan's list of the tiles that are not hidden (on RGBA8: the span records cut from it),
+        // per eye pass like the upscale launches in front of it; all on the caller's stream
+        EyePass passes[2];
+        const int np = EyePasses(n, firstEye, alternate, passes);
+        hipError_t e = hipSuccess;
+        for (int p = 0; p < np && e == hipSuccess; ++p) {
+            const EyePass &ps = passes[p];
+            if (!plan_.nRcas[ps.eye]) continue;
+            RcasArgs b = a;
+            ps.Select(b);
+            b.tileList = RcasList(ps.eye);
+            if (spanRecDev_ && plan_.nSpans[ps.eye]) { b.spanRec = SpanRecords(ps.eye); b.nSpans = plan_.nSpans[ps.eye]; }
+            e = launch_rcas(plan_.rcasPrec, (int)in.format, (int)out.format, b, ps.cnt, stream, plan_.nRcas[ps.eye]);
+        }
+        return Launched(e, "RCAS");
+    }
     return Launched(launch_rcas(plan_.rcasPrec, (int)in.format, (int)out.format, a, n, stream), "RCAS");
 }
 
@@ -703,8 +745,12 @@ int PostProcessor::Apply(int eye, const ovrfsr_image *in, const ovrfsr_bounds *b
         // (pair mode: both eyes' results are alive at once -- two ctx-owned images, left first)
         const size_t one = (size_t)dst.pitch_bytes * dst.height;
         if (pairMode && sharpened_.bytes < 2 * one) { rc = FlushPending(stream); if (rc != OVRFSR_OK) return rc; } // (cannot grow under a recorded eye)
+        const size_t had = sharpened_.bytes;
         rc = EnsureBuffer(sharpened_, pairMode ? 2 * one : one);
         if (rc != OVRFSR_OK) return rc;
+        // under a hidden-area mesh the skipped tiles are never written: the ctx-owned image starts out as zeros, once, when it is allocated
+        if (plan_.hiddenArea && sharpened_.bytes != had && hipMemsetAsync(sharpened_.p, 0, sharpened_.bytes, stream) != hipSuccess)
+            return Fail(OVRFSR_ERR_HIP, "clearing the ctx-owned output image failed");
         dst.data = pairMode && eye == OVRFSR_EYE_RIGHT ? static_cast<uint8_t *>(sharpened_.p) + one : sharpened_.p;
     }
     // an in-place call would race: RCAS / NVSharpen / EASU read neighbour texels other workgroups overwrite.  Checked against the

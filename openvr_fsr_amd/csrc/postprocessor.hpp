@@ -41,6 +41,9 @@ public:
     const ovrfsr_config &GetConfig() const { return cfg_; }
     const char *LastError() const { return lastError_.c_str(); }
     bool PairPending() const { return sequence_.PairPending(); }
+    // ovrfsr_set_hidden_area / ovrfsr_hidden_area_stats behind their argument checks
+    int SetHiddenArea(int eye, const float *uv, uint32_t triangles);
+    int HiddenAreaStats(int eye, uint32_t *tilesTotal, uint32_t *tilesSkipped);
     int LastGpuTimeMs(float *ms);
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
@@ -48,6 +51,7 @@ private:
     int device_;
     ovrfsr_config cfg_;
     std::string lastError_;
+    std::vector<float> hiddenUv_[2]; // the hidden-area mesh of each eye, 6 floats per triangle: outlives Reset and SetConfig (header)
 
     // PostProcessor.h:16-24
     bool enabled_ = true;
@@ -121,6 +125,7 @@ private:
     const uint32_t *InsideList(int eye) const { return tileListDev_ + plan_.listOffInside[eye]; }
     const uint32_t *OutsideList(int eye) const { return tileListDev_ + plan_.listOffOutside[eye]; }
     const uint32_t *OutsideRecords(int eye) const { return tileRecDev_ + 4 * plan_.listOffOutside[eye]; }
+    const uint32_t *RcasList(int eye) const { return tileListDev_ + plan_.listOffRcas[eye]; } // (two-pass under a hidden-area mesh)
     const uint32_t *SpanRecords(int eye) const { return spanRecDev_ + 2 * plan_.spanOff[eye]; }
     int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
     template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;

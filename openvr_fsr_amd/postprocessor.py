@@ -120,6 +120,18 @@ class PostProcessor:
         """cfg.pair_submit: did the last apply only record its submission (ovrfsr_pair_pending)?"""
         return bool(self._lib.ovrfsr_pair_pending(self._ctx))
 
+    def set_hidden_area(self, eye, uv):
+        """ovrfsr_set_hidden_area: one eye's hidden-area mesh, anything that reshapes to [n, 3, 2] (u, v in [0,1] of that eye's image, v = 0 the
+        first stored row); None or an empty mesh clears it.  The next apply rebuilds."""
+        m, n = K.mesh_array(uv)
+        self._check(self._lib.ovrfsr_set_hidden_area(self._ctx, int(eye), m.ctypes.data_as(C.POINTER(C.c_float)) if n else None, n))
+
+    def hidden_area_stats(self, eye):
+        """ovrfsr_hidden_area_stats, after an apply: (tiles per image of that eye's list, tiles of them the current plan skips)."""
+        total, skipped = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.ovrfsr_hidden_area_stats(self._ctx, int(eye), C.byref(total), C.byref(skipped)))
+        return total.value, skipped.value
+
     def last_gpu_time_ms(self):
         ms = C.c_float()
         self._check(self._lib.ovrfsr_last_gpu_time_ms(self._ctx, C.byref(ms)))

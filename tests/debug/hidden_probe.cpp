@@ -1,0 +1,140 @@
+// tests/debug/hidden_probe.cpp -- the planner under a hidden-area mesh (csrc/pipeline_plan.cpp, HiddenArea) on its own: no HIP, no device.
+// tests/test_hidden_area.py compiles this file with pipeline_plan.cpp, constants.cpp and nis_config.cpp under -fsanitize=address,undefined
+// and runs it as a child.
+//
+//   hidden_probe CASES           one JSON line per line of the file CASES: the case line of tests/debug/plan_probe.cpp, followed by
+//       trianglesLeft trianglesRight and then 6 floats (u v u v u v) per triangle, the left mesh first
+//   Each line reports
+//     "no_mesh_equal"   the plan of the six-argument call and the plan of the call with an EMPTY mesh, serialised field by field, are equal
+//     "form", "form_plain"   the form with the mesh and of the six-argument call
+//     "tile_lists", "hidden_area", "lists_shared", "tiles", "tile" [w, h], "skipped" [l, r]
+//     "inside", "ring", "outside", "rcas"   per eye, the tile indices of each list segment as the plan holds them
+//     "spans"           per eye, [x0, tileRow, xEnd] of every RCAS segment
+//     "hidden"          per eye, the tile map the rule gives for the planned output size (hidden_tiles), row-major
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+#include "../../openvr_fsr_amd/csrc/pipeline_plan.h"
+
+using namespace ovrfsr;
+
+template <class T>
+static void put(std::string &s, const T *v, size_t n)
+{
+    s.append(reinterpret_cast<const char *>(v), n * sizeof(T));
+    s += '|';
+}
+template <class T> static void put(std::string &s, const T &v) { put(s, &v, 1); }
+
+// every field of a Plan, in declaration order
+static std::string serialised(const Plan &p)
+{
+    std::string s;
+    put(s, p.inputWidth); put(s, p.inputHeight); put(s, p.inputFormat); put(s, p.onlyOneEye); put(s, p.outputWidth); put(s, p.outputHeight);
+    put(s, p.doUpscale); put(s, p.doSharpen); put(s, p.useNis); put(s, (int)p.form); put(s, p.tileLists); put(s, p.maskLists); put(s, p.hiddenArea);
+    put(s, p.overlapOutside); put(s, p.pipelineFormat); put(s, p.intermediateFormat); put(s, p.ownedFormat); put(s, p.launchPrec); put(s, p.rcasPrec);
+    put(s, p.easuCon, 16); put(s, p.rcasCon, 4);
+    put(s, reinterpret_cast<const unsigned char *>(&p.nis), sizeof p.nis);
+    put(s, &p.centre[0][0], 8); put(s, p.radius, 4); put(s, p.maskMode, 2); put(s, p.tieHalfMin); put(s, p.unorm8StoreGuard);
+    put(s, p.cellsW); put(s, p.cellsH); put(s, p.fusedCellsW); put(s, p.fusedCellsH); put(s, p.nisCellsW); put(s, p.nisCellsH);
+    put(s, p.rcpOut, 2); put(s, p.rcpExact);
+    for (const BilinTap &t : p.taps) { put(s, t.i0); put(s, t.frac); }
+    put(s, p.tapYOff); put(s, p.outsideCols); put(s, p.outsideRows, 2);
+    put(s, p.lists.data(), p.lists.size()); put(s, p.recs.data(), p.recs.size()); put(s, p.spans.data(), p.spans.size());
+    put(s, p.nInside, 2); put(s, p.nOutside, 2); put(s, p.nRing, 2); put(s, p.nSpans, 2);
+    put(s, p.listOffInside, 2); put(s, p.listOffOutside, 2); put(s, p.listOffRing, 2); put(s, p.spanOff, 2);
+    put(s, p.listsShared); put(s, p.nSkipped, 2);
+    return s;
+}
+
+static void print_list(const char *name, const Plan &p, const size_t off[2], const uint32_t n[2])
+{
+    std::printf(", \"%s\": [", name);
+    for (int eye = 0; eye < 2; ++eye) {
+        std::printf("%s[", eye ? ", " : "");
+        for (uint32_t i = 0; i < n[eye]; ++i) std::printf("%s%u", i ? ", " : "", p.lists[off[eye] + i]);
+        std::printf("]");
+    }
+    std::printf("]");
+}
+
+int main(int argc, char **argv)
+{
+    if (argc != 2) {
+        std::fprintf(stderr, "usage: hidden_probe CASES\n");
+        return 2;
+    }
+    std::ifstream f(argv[1]);
+    if (!f) {
+        std::fprintf(stderr, "cannot read %s\n", argv[1]);
+        return 2;
+    }
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.empty()) continue;
+        std::istringstream in(line);
+        std::string id;
+        uint32_t format, w, h, count[2];
+        int oneEye;
+        long dest;
+        ovrfsr_config c;
+        std::memset(&c, 0, sizeof c);
+        c.struct_size = sizeof c;
+        in >> id >> format >> w >> h >> oneEye >> dest >> c.fsr_enabled >> c.use_nis >> c.debug_mode >> c.render_scale >> c.sharpness >> c.radius >>
+            c.proj_centre[0] >> c.proj_centre[1] >> c.proj_centre[2] >> c.proj_centre[3] >> c.out_width >> c.out_height >> c.precision >>
+            c.quantize_intermediate >> c.fused >> c.stage_mask >> c.pair_submit >> c.reference_formats >> count[0] >> count[1];
+        std::vector<float> uv[2];
+        for (int eye = 0; eye < 2 && in; ++eye) {
+            uv[eye].resize(6 * (size_t)count[eye]);
+            for (float &x : uv[eye]) in >> x;
+        }
+        if (!in) {
+            std::fprintf(stderr, "malformed case line: %s\n", line.c_str());
+            return 2;
+        }
+        Plan plain, empty, p;
+        const HiddenArea none;
+        HiddenArea mesh;
+        for (int eye = 0; eye < 2; ++eye) { mesh.uv[eye] = uv[eye].data(); mesh.triangles[eye] = count[eye]; }
+        const Refusal r0 = plan_pipeline(c, format, w, h, oneEye != 0, &plain);
+        const Refusal r1 = plan_pipeline(c, format, w, h, oneEye != 0, &empty, &none);
+        const Refusal r = plan_pipeline(c, format, w, h, oneEye != 0, &p, &mesh);
+        std::printf("{\"id\": \"%s\", \"status\": %d, \"no_mesh_equal\": %d", id.c_str(), r.status,
+                    (int)(r0.status == r1.status && r0.status == r.status && serialised(plain) == serialised(empty)));
+        if (!r) {
+            const uint32_t tw = 32, th = p.useNis && p.doUpscale ? 24 : 32;
+            const uint32_t tx = (p.outputWidth + tw - 1) / tw, ty = (p.outputHeight + th - 1) / th;
+            std::printf(", \"form\": \"%s\", \"form_plain\": \"%s\", \"out\": [%u, %u], \"tile_lists\": %d, \"hidden_area\": %d, \"lists_shared\": %d, "
+                        "\"tiles\": %u, \"tile\": [%u, %u], \"skipped\": [%u, %u]", form_name(p.form), form_name(plain.form), p.outputWidth, p.outputHeight,
+                        (int)p.tileLists, (int)p.hiddenArea, (int)p.listsShared, tx * ty, tw, th, p.nSkipped[0], p.nSkipped[1]);
+            print_list("inside", p, p.listOffInside, p.nInside);
+            print_list("ring", p, p.listOffRing, p.nRing);
+            print_list("outside", p, p.listOffOutside, p.nOutside);
+            print_list("rcas", p, p.listOffRcas, p.nRcas);
+            std::printf(", \"spans\": [");
+            for (int eye = 0; eye < 2; ++eye) {
+                std::printf("%s[", eye ? ", " : "");
+                for (uint32_t i = 0; i < p.nSpans[eye]; ++i) {
+                    const uint32_t a = p.spans[2 * (p.spanOff[eye] + i)], xEnd = p.spans[2 * (p.spanOff[eye] + i) + 1];
+                    std::printf("%s[%u, %u, %u]", i ? ", " : "", a & 0xffffu, a >> 16, xEnd);
+                }
+                std::printf("]");
+            }
+            std::printf("], \"hidden\": [");
+            std::vector<uint8_t> map((size_t)tx * ty);
+            for (int eye = 0; eye < 2; ++eye) {
+                if (oneEye) hidden_tiles(mesh.uv[eye], mesh.triangles[eye], nullptr, 0, false, p.outputWidth, p.outputHeight, tw, th, map.data());
+                else hidden_tiles(mesh.uv[0], mesh.triangles[0], mesh.uv[1], mesh.triangles[1], true, p.outputWidth, p.outputHeight, tw, th, map.data());
+                std::printf("%s[", eye ? ", " : "");
+                for (size_t i = 0; i < map.size(); ++i) std::printf("%s%u", i ? ", " : "", map[i]);
+                std::printf("]");
+            }
+            std::printf("]");
+        }
+        std::printf("}\n");
+    }
+    return 0;
+}
