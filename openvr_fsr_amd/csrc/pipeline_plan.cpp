@@ -95,7 +95,7 @@ void easu_footprints(Plan &p)
     p.fusedCellsH = extentRing(p.outputHeight, kTileH, sy, cy);
 }
 
-// LDS footprint of one 32x24 NVScaler group
+// LDS footprint of one NVScaler group (32x24: p.grid)
 void nis_footprints(Plan &p)
 {
     auto extent = [](uint32_t outN, int blk, float s) {
@@ -107,8 +107,8 @@ void nis_footprints(Plan &p)
         }
         return best;
     };
-    p.nisCellsW = extent(p.outputWidth, 32, p.nis.kScaleX);
-    p.nisCellsH = extent(p.outputHeight, 24, p.nis.kScaleY);
+    p.nisCellsW = extent(p.outputWidth, (int)p.grid.tileW, p.nis.kScaleX);
+    p.nisCellsH = extent(p.outputHeight, (int)p.grid.tileH, p.nis.kScaleY);
 }
 
 // o/outW, o/outH of the bilinear fallback as a multiply and two FMAs: verify against IEEE division for every o
@@ -272,136 +272,184 @@ void hidden_tiles(const float *left, uint32_t leftTriangles, const float *right,
 
 namespace {
 
-// The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one mask group
-// inside the radius (EASU kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel).
-// `hidden` (a hidden-area mesh is set; null: none): per eye, the tiles no lens shows.  They are in neither list.  `classify` = false (no
-// mixed mask: the lists exist for the mesh alone): every other tile is an "inside" tile, whatever the radius -- the kernel that runs on it
-// is the one the launch without lists runs, mask test included.  In the two-kernel forms (`rcasForm`: Form::MaskSorted, Form::TwoPass) a
-// hidden tile 4-adjacent to a tile RCAS processes joins the ring, so that EASU still writes the intermediate texels RCAS's cross taps read.
-void tile_lists(Plan &p, uint32_t tileW, uint32_t tileH, uint32_t groupW, uint32_t groupH, const std::vector<uint8_t> *hidden = nullptr,
-                bool classify = true, Form rcasForm = Form::None)
+// ---- the tile lists ----------------------------------------------------------------------------------------------------------------------
+// The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one mask group inside the radius (EASU
+// kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel); under a hidden-area mesh, the tiles no lens shows are in
+// neither list.  tile_lists() builds them in the steps below, each with one job; all of them run at plan time only.
+
+// one eye's tiles by class, each in raster order
+struct TileClasses {
+    std::vector<uint32_t> inside, outside, hidden;
+};
+// per eye, a byte per tile of the grid (hidden_tiles); empty: no mesh in effect
+struct HiddenMaps {
+    std::vector<uint8_t> eye[2];
+};
+
+// one eye per texture: each eye's own mesh; a shared side-by-side texture: one map of both halves, the same for both "eyes"
+HiddenMaps hidden_maps(const Plan &p, const HiddenArea &mesh)
 {
+    const TileGrid &g = p.grid;
+    HiddenMaps maps;
+    maps.eye[0].resize(g.tiles());
+    if (p.onlyOneEye) {
+        maps.eye[1].resize(g.tiles());
+        for (int eye = 0; eye < 2; ++eye)
+            hidden_tiles(mesh.uv[eye], mesh.triangles[eye], nullptr, 0, false, p.outputWidth, p.outputHeight, g.tileW, g.tileH, maps.eye[eye].data());
+    } else {
+        hidden_tiles(mesh.uv[0], mesh.triangles[0], mesh.uv[1], mesh.triangles[1], true, p.outputWidth, p.outputHeight, g.tileW, g.tileH, maps.eye[0].data());
+        maps.eye[1] = maps.eye[0];
+    }
+    return maps;
+}
+
+// Step 1.  `hidden` (empty: none) takes its tiles out first.  `byRadius` = false (no mixed mask: the lists exist for the mesh alone): every
+// other tile is an "inside" tile, whatever the radius -- the kernel that runs on it is the one the launch without lists runs, mask test included.
+TileClasses classify_tiles(const TileGrid &g, const uint32_t centre[4], uint32_t r2, bool byRadius, const std::vector<uint8_t> &hidden)
+{
+    const uint32_t gpx = g.tileW / g.groupW, gpy = g.tileH / g.groupH; // mask groups per tile
+    TileClasses c;
+    for (uint32_t t = 0; t < g.tiles(); ++t) {
+        if (!hidden.empty() && hidden[t]) { c.hidden.push_back(t); continue; }
+        const uint32_t tyi = t / g.tx, txi = t - tyi * g.tx;
+        bool any = !byRadius;
+        for (uint32_t k = 0; k < gpx * gpy && !any; ++k) {
+            const uint32_t gx = gpx * txi + (k % gpx), gy = gpy * tyi + (k / gpx);
+            const uint32_t cx = gx * g.groupW + g.groupW / 2, cy = gy * g.groupH + g.groupH / 2;
+            const uint32_t ax = centre[0] - cx, ay = centre[1] - cy, bx = centre[2] - cx, by = centre[3] - cy;
+            any = (ax * ax + ay * ay <= r2) || (bx * bx + by * by <= r2);
+        }
+        (any ? c.inside : c.outside).push_back(t);
+    }
+    return c;
+}
+
+// Step 2.  What RCAS walks, in raster order: the inside tiles -- in the two-pass form under a mesh (`everyVisibleTile`; without a mesh that
+// form runs RCAS over the whole image, with no list), every tile that is not hidden.
+std::vector<uint32_t> rcas_tiles(const TileClasses &c, bool everyVisibleTile)
+{
+    std::vector<uint32_t> r = c.inside;
+    if (everyVisibleTile) {
+        r.insert(r.end(), c.outside.begin(), c.outside.end());
+        std::sort(r.begin(), r.end());
+    }
+    return r;
+}
+
+// The ring's candidates, in the order the ring lists them: the outside tiles -- their intermediate is nobody else's.  In the two-kernel forms
+// under a mesh a hidden tile next to a tile RCAS processes joins them (`hiddenToo`: mask-sorted), so that EASU still writes the intermediate
+// texels RCAS's cross taps read (a hidden ring tile is still a skipped one: nothing of the destination is written there).  Two-pass under a
+// mesh (`rcasOwnList`): the outside tiles' intermediate is the outside-tile launch's, so the candidates are the hidden tiles only.
+std::vector<uint32_t> ring_candidates(const TileClasses &c, bool rcasOwnList, bool hiddenToo)
+{
+    std::vector<uint32_t> v;
+    if (!rcasOwnList) v = c.outside;
+    if (rcasOwnList || hiddenToo) v.insert(v.end(), c.hidden.begin(), c.hidden.end());
+    return v;
+}
+
+// Step 3.  The candidates that share an edge with a tile of `rcas`, in the candidates' order: RCAS's cross taps reach one pixel across a tile
+// edge, so the EASU launch has to write the intermediate there too.
+std::vector<uint32_t> ring_tiles(const TileGrid &g, const std::vector<uint32_t> &rcas, const std::vector<uint32_t> &candidates)
+{
+    const uint32_t tx = g.tx, ty = g.ty;
+    std::vector<uint8_t> isIn(g.tiles(), 0);
+    for (uint32_t t : rcas) isIn[t] = 1;
+    std::vector<uint32_t> ring;
+    for (uint32_t t : candidates) {
+        const uint32_t tyi = t / tx, txi = t - tyi * tx;
+        if ((txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx])) ring.push_back(t);
+    }
+    return ring;
+}
+
+// Step 4.  RCAS on RGBA8 walks spans, not tiles (rcas_dpp_kernel<.., true>): per 32-row band, runs of adjacent tiles of `rcas` (row-major
+// here), cut into the kernel's 62-column segments {x0 | tileY << 16, xEnd}, appended to `spans`.  Every XCD then gets a contiguous raster run
+// of segments (xcd_source), so that the 128-byte lines two neighbouring segments share, and the rows two bands share, are fetched once.
+// *first, *count: where the eye's segments start in `spans` (in segments) and how many they are.
+void rcas_spans(const TileGrid &g, uint32_t outW, const std::vector<uint32_t> &rcas, std::vector<uint32_t> &spans, size_t *first, uint32_t *count)
+{
+    const size_t off = *first = spans.size() / 2;
+    for (size_t i = 0; i < rcas.size();) {
+        size_t j = i;
+        while (j + 1 < rcas.size() && rcas[j + 1] == rcas[j] + 1 && (rcas[j + 1] / g.tx) == (rcas[i] / g.tx)) ++j;
+        const uint32_t tyi = rcas[i] / g.tx, xa = (rcas[i] - tyi * g.tx) * g.tileW;
+        const uint32_t xb = std::min((rcas[j] - tyi * g.tx + 1) * g.tileW, outW);
+        for (uint32_t x0 = xa; x0 < xb; x0 += kRcasDppTileW) {
+            spans.push_back(x0 | (tyi << 16));
+            spans.push_back(std::min(x0 + (uint32_t)kRcasDppTileW, xb));
+        }
+        i = j + 1;
+    }
+    const uint32_t n = *count = (uint32_t)(spans.size() / 2 - off);
+    std::vector<uint32_t> r(2 * (size_t)n);
+    for (uint32_t b = 0; b < n; ++b) {
+        const size_t src = off + xcd_source(b, n);
+        r[2 * (size_t)b] = spans[2 * src]; r[2 * (size_t)b + 1] = spans[2 * src + 1];
+    }
+    std::copy(r.begin(), r.end(), spans.begin() + 2 * off);
+}
+
+// Step 5.  Writes one eye's part of the plan: its segments behind what p.lists holds already, with their counts and offsets: inside | ring | outside, and `rcas` as a
+// fourth where RCAS has a list of its own (null: it walks the inside segment).  Inside, outside and rcas in XCD order; the ring keeps the
+// order it was found in.
+void pack_lists(Plan &p, int eye, const TileClasses &c, const std::vector<uint32_t> &ring, const std::vector<uint32_t> *rcas)
+{
+    auto append = [&p](const std::vector<uint32_t> &v, bool xcdOrder, size_t &off, uint32_t &n) {
+        off = p.lists.size();
+        n = (uint32_t)v.size();
+        for (uint32_t b = 0; b < n; ++b) p.lists.push_back(v[xcdOrder ? xcd_source(b, n) : b]);
+    };
+    append(c.inside, true, p.listOffInside[eye], p.nInside[eye]);
+    append(ring, false, p.listOffRing[eye], p.nRing[eye]);
+    append(c.outside, true, p.listOffOutside[eye], p.nOutside[eye]);
+    p.listOffRcas[eye] = p.listOffInside[eye]; p.nRcas[eye] = p.nInside[eye];
+    if (rcas) append(*rcas, true, p.listOffRcas[eye], p.nRcas[eye]);
+    p.nSkipped[eye] = (uint32_t)c.hidden.size();
+}
+
+// Step 6.  One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin (first
+// column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of dependent scalar loads: tile
+// index -> tap tables).  Reads the plan's grid, tap tables and lists; writes nothing of it.
+std::vector<uint32_t> outside_records(const Plan &p)
+{
+    const TileGrid &g = p.grid;
     const uint32_t outW = p.outputWidth, outH = p.outputHeight;
-    const uint32_t tx = (outW + tileW - 1) / tileW, ty = (outH + tileH - 1) / tileH;
-    const uint32_t gpx = tileW / groupW, gpy = tileH / groupH; // mask groups per tile
-    std::vector<uint32_t> &lists = p.lists, &spans = p.spans;
-    std::vector<uint32_t> in[2], outl[2], rcas[2];
-    p.nTiles = tx * ty;
-    for (int eye = 0; eye < 2; ++eye) {
-        const uint32_t *c = p.centre[eye];
-        for (uint32_t t = 0; t < tx * ty; ++t) {
-            if (hidden && hidden[eye][t]) { ++p.nSkipped[eye]; continue; }
-            const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            bool any = !classify;
-            for (uint32_t g = 0; g < gpx * gpy && !any; ++g) {
-                const uint32_t gx = gpx * txi + (g % gpx), gy = gpy * tyi + (g / gpx);
-                const uint32_t cx = gx * groupW + groupW / 2, cy = gy * groupH + groupH / 2;
-                const uint32_t ax = c[0] - cx, ay = c[1] - cy, bx = c[2] - cx, by = c[3] - cy;
-                any = (ax * ax + ay * ay <= p.radius[1]) || (bx * bx + by * by <= p.radius[1]);
-            }
-            (any ? in[eye] : outl[eye]).push_back(t);
-        }
+    std::vector<uint32_t> recs(p.lists.size() * 4, 0u);
+    const BilinTap *bx = p.taps.data(), *by = p.taps.data() + p.tapYOff;
+    const uint32_t rowsCap = p.outsideRows[g.tileH == (uint32_t)kTileH ? 0 : 1];
+    for (size_t i = 0; i < p.lists.size(); ++i) {
+        const uint32_t t = p.lists[i], tyi = t / g.tx, txi = t - tyi * g.tx;
+        const uint32_t ox0 = txi * g.tileW, oy0 = tyi * g.tileH;
+        const int X0 = bx[ox0].i0, Y0 = by[oy0].i0;
+        const int colsN = std::min<int>((int)p.outsideCols, bx[std::min(ox0 + g.tileW - 1, outW - 1)].i0 + 2 - X0);
+        const int rowsN = std::min<int>((int)rowsCap, by[std::min(oy0 + g.tileH - 1, outH - 1)].i0 + 2 - Y0);
+        recs[4 * i + 0] = ox0 | (oy0 << 16);
+        recs[4 * i + 1] = (uint32_t)(X0 + 1) | ((uint32_t)(Y0 + 1) << 16);
+        recs[4 * i + 2] = (uint32_t)colsN | ((uint32_t)rowsN << 8);
     }
-    // what RCAS walks, in raster order: the inside tiles -- in the two-pass form under a mesh, every tile that is not hidden
-    const bool rcasOwnList = hidden && rcasForm == Form::TwoPass;
-    for (int eye = 0; eye < 2; ++eye) {
-        rcas[eye] = in[eye];
-        if (rcasOwnList) {
-            rcas[eye].insert(rcas[eye].end(), outl[eye].begin(), outl[eye].end());
-            std::sort(rcas[eye].begin(), rcas[eye].end());
-        }
-    }
+    return recs;
+}
+
+// The six steps, per eye, over p.grid; what steers them is the plan's own: maskLists, hiddenArea (with `hidden`, its per-eye maps) and form.
+void tile_lists(Plan &p, const HiddenMaps &hidden)
+{
+    const TileGrid &g = p.grid;
+    // two-pass under a mesh: RCAS gets a list of its own.  Spans: wherever the tiles are the span kernel's and its packing holds them
+    const bool rcasOwnList = p.hiddenArea && p.form == Form::TwoPass;
+    const bool cutSpans = g.tileW == (uint32_t)kTileW && g.tileH == (uint32_t)kRcasDppTileH && p.outputWidth < 65536u && g.ty < 65536u;
+    TileClasses c[2];
     std::vector<uint32_t> ring[2];
     for (int eye = 0; eye < 2; ++eye) {
-        std::vector<uint8_t> isIn((size_t)tx * ty, 0);
-        auto adjacent = [&](uint32_t t) {
-            const uint32_t tyi = t / tx, txi = t - tyi * tx;
-            return (txi > 0 && isIn[t - 1]) || (txi + 1 < tx && isIn[t + 1]) || (tyi > 0 && isIn[t - tx]) || (tyi + 1 < ty && isIn[t + tx]);
-        };
-        if (rcasOwnList) { // (the outside tiles' intermediate is the outside-tile launch's: the ring holds hidden tiles only)
-            for (uint32_t t : rcas[eye]) isIn[t] = 1;
-            for (uint32_t t = 0; t < tx * ty; ++t)
-                if (hidden[eye][t] && adjacent(t)) ring[eye].push_back(t);
-            continue;
-        }
-        for (uint32_t t : in[eye]) isIn[t] = 1;
-        for (uint32_t t : outl[eye])
-            if (adjacent(t)) ring[eye].push_back(t);
-        if (hidden && rcasForm == Form::MaskSorted) {
-            for (uint32_t t = 0; t < tx * ty; ++t)
-                if (hidden[eye][t] && adjacent(t)) ring[eye].push_back(t);
-        } // (a hidden ring tile is still a skipped one: nothing of the destination is written there)
+        c[eye] = classify_tiles(g, p.centre[eye], p.radius[1], p.maskLists, hidden.eye[eye]);
+        const std::vector<uint32_t> rcas = rcas_tiles(c[eye], rcasOwnList);
+        ring[eye] = ring_tiles(g, rcas, ring_candidates(c[eye], rcasOwnList, p.hiddenArea && p.form == Form::MaskSorted));
+        if (cutSpans) rcas_spans(g, p.outputWidth, rcas, p.spans, &p.spanOff[eye], &p.nSpans[eye]);
+        pack_lists(p, eye, c[eye], ring[eye], rcasOwnList ? &rcas : nullptr);
     }
-    p.listsShared = in[0] == in[1];
-    if (hidden) p.listsShared = p.listsShared && outl[0] == outl[1] && ring[0] == ring[1]; // (the final lists: without a mesh they follow from in[])
-    // RCAS on the mask-sorted form (RGBA8): per 32-row band, runs of adjacent tiles touching the radius, cut into the DPP
-    // kernel's 62-column segments (rcas_dpp_kernel<.., true>): {x0 | tileY << 16, xEnd}
-    if (tileW == (uint32_t)kTileW && tileH == (uint32_t)kRcasDppTileH && outW < 65536u && ty < 65536u) {
-        for (int eye = 0; eye < 2; ++eye) {
-            const std::vector<uint32_t> &run = rcas[eye]; // row-major here
-            p.spanOff[eye] = spans.size() / 2;
-            for (size_t i = 0; i < run.size();) {
-                size_t j = i;
-                while (j + 1 < run.size() && run[j + 1] == run[j] + 1 && (run[j + 1] / tx) == (run[i] / tx)) ++j;
-                const uint32_t tyi = run[i] / tx, xa = (run[i] - tyi * tx) * tileW;
-                const uint32_t xb = std::min((run[j] - tyi * tx + 1) * tileW, outW);
-                for (uint32_t x0 = xa; x0 < xb; x0 += kRcasDppTileW) {
-                    spans.push_back(x0 | (tyi << 16));
-                    spans.push_back(std::min(x0 + (uint32_t)kRcasDppTileW, xb));
-                }
-                i = j + 1;
-            }
-            p.nSpans[eye] = (uint32_t)(spans.size() / 2 - p.spanOff[eye]);
-            // every XCD a contiguous raster run of segments (xcd_source), so that the 128-byte lines two neighbouring
-            // segments share, and the rows two bands share, are fetched once
-            const uint32_t n = p.nSpans[eye];
-            std::vector<uint32_t> r(2 * (size_t)n);
-            for (uint32_t b = 0; b < n; ++b) {
-                const size_t src = p.spanOff[eye] + xcd_source(b, n);
-                r[2 * (size_t)b] = spans[2 * src]; r[2 * (size_t)b + 1] = spans[2 * src + 1];
-            }
-            std::copy(r.begin(), r.end(), spans.begin() + 2 * p.spanOff[eye]);
-        }
-    }
-    auto xcd_order = [](std::vector<uint32_t> &v) {
-        const uint32_t n = (uint32_t)v.size();
-        std::vector<uint32_t> r(n);
-        for (uint32_t b = 0; b < n; ++b) r[b] = v[xcd_source(b, n)];
-        v.swap(r);
-    };
-    for (int eye = 0; eye < 2; ++eye) {
-        xcd_order(in[eye]); xcd_order(outl[eye]);
-        p.nInside[eye] = (uint32_t)in[eye].size(); p.nOutside[eye] = (uint32_t)outl[eye].size();
-        // inside | ring | outside: the ring tiles follow the inside tiles so that ONE EASU launch over nInside + nRing entries
-        // also writes the bilinear intermediate of the ring (its all-outside path), while RCAS walks the first nInside only
-        p.listOffInside[eye] = lists.size(); lists.insert(lists.end(), in[eye].begin(), in[eye].end());
-        p.nRing[eye] = (uint32_t)ring[eye].size();
-        p.listOffRing[eye] = lists.size(); lists.insert(lists.end(), ring[eye].begin(), ring[eye].end());
-        p.listOffOutside[eye] = lists.size(); lists.insert(lists.end(), outl[eye].begin(), outl[eye].end());
-        // RCAS: the inside list, or (two-pass under a mesh) a fourth segment of its own
-        p.nRcas[eye] = p.nInside[eye]; p.listOffRcas[eye] = p.listOffInside[eye];
-        if (rcasOwnList) {
-            xcd_order(rcas[eye]);
-            p.nRcas[eye] = (uint32_t)rcas[eye].size();
-            p.listOffRcas[eye] = lists.size(); lists.insert(lists.end(), rcas[eye].begin(), rcas[eye].end());
-        }
-    }
-    // One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin
-    // (first column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of
-    // dependent scalar loads: tile index -> tap tables)
-    p.recs.assign(lists.size() * 4, 0u);
-    const BilinTap *bx = p.taps.data(), *by = p.taps.data() + p.tapYOff;
-    const uint32_t rowsCap = p.outsideRows[tileH == 24 ? 1 : 0];
-    for (size_t i = 0; i < lists.size(); ++i) {
-        const uint32_t t = lists[i], tyi = t / tx, txi = t - tyi * tx;
-        const uint32_t ox0 = txi * tileW, oy0 = tyi * tileH;
-        const int X0 = bx[ox0].i0, Y0 = by[oy0].i0;
-        const int colsN = std::min<int>((int)p.outsideCols, bx[std::min(ox0 + tileW - 1, outW - 1)].i0 + 2 - X0);
-        const int rowsN = std::min<int>((int)rowsCap, by[std::min(oy0 + tileH - 1, outH - 1)].i0 + 2 - Y0);
-        p.recs[4 * i + 0] = ox0 | (oy0 << 16);
-        p.recs[4 * i + 1] = (uint32_t)(X0 + 1) | ((uint32_t)(Y0 + 1) << 16);
-        p.recs[4 * i + 2] = (uint32_t)colsN | ((uint32_t)rowsN << 8);
-    }
+    // (the final lists: without a mesh outside and ring follow from inside)
+    p.listsShared = c[0].inside == c[1].inside && c[0].outside == c[1].outside && ring[0] == ring[1];
+    p.recs = outside_records(p);
 }
 
 // Near-tie guard of a half-float intermediate: the smallest value whose flipped half rounding could exceed the 1e-3 tolerance
@@ -423,6 +471,18 @@ const Refusal *plan_refusals(size_t *count)
 {
     *count = R_COUNT;
     return kRefusals;
+}
+
+TileGrid tile_grid(bool useNis, bool doUpscale, uint32_t outW, uint32_t outH)
+{
+    TileGrid g;
+    g.tileW = (uint32_t)kTileW;
+    g.tileH = useNis && doUpscale ? 24u : (uint32_t)kTileH; // NVScaler's groups; NVSharpen dispatches 32x32 (PostProcessor.cpp:397,:492)
+    g.groupW = useNis ? g.tileW : 16u;
+    g.groupH = useNis ? g.tileH : 16u;
+    g.tx = (outW + g.tileW - 1) / g.tileW;
+    g.ty = (outH + g.tileH - 1) / g.tileH;
+    return g;
 }
 
 const char *form_name(Form f)
@@ -491,6 +551,7 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     if (cfg.stage_mask == 2) p.doUpscale = false;
     if (cfg.stage_mask < 0 || cfg.stage_mask > 2) return kRefusals[R_STAGE_MASK];
     if (!p.doUpscale && (ow != width || oh != height)) return kRefusals[R_SHARPEN_ONLY_SIZE];
+    p.grid = tile_grid(p.useNis, p.doUpscale, ow, oh);
     if (cfg.precision != OVRFSR_PRECISION_FP32 && cfg.precision != OVRFSR_PRECISION_FP32_STRICT && cfg.precision != OVRFSR_PRECISION_FP32_EXACT)
         return kRefusals[R_PRECISION];
     const bool exact = cfg.precision == OVRFSR_PRECISION_FP32_EXACT, both = p.doUpscale && p.doSharpen;
@@ -578,24 +639,7 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     v.inW = (int32_t)width; v.inH = (int32_t)height; v.outW = (int32_t)ow; v.outH = (int32_t)oh;
     p.overlapOutside = p.maskLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
 
-    if (p.tileLists) {
-        // NVScaler: one workgroup per 32x24 mask group; EASU: 32x32 tiles of four 16x16 groups
-        const uint32_t tileW = 32, tileH = cfg.use_nis ? 24 : (uint32_t)kTileH;
-        if (!p.hiddenArea) {
-            tile_lists(p, tileW, tileH, cfg.use_nis ? 32 : 16, cfg.use_nis ? 24 : 16);
-        } else {
-            // one eye per texture: each eye's own mesh; a shared side-by-side texture: one map of both halves, the same for both "eyes"
-            const uint32_t tiles = ((ow + tileW - 1) / tileW) * ((oh + tileH - 1) / tileH);
-            std::vector<uint8_t> map[2];
-            for (int eye = 0; eye < 2; ++eye) {
-                map[eye].resize(tiles);
-                if (onlyOneEye) hidden_tiles(hidden->uv[eye], hidden->triangles[eye], nullptr, 0, false, ow, oh, tileW, tileH, map[eye].data());
-                else if (eye == 0) hidden_tiles(hidden->uv[0], hidden->triangles[0], hidden->uv[1], hidden->triangles[1], true, ow, oh, tileW, tileH, map[0].data());
-                else map[1] = map[0];
-            }
-            tile_lists(p, tileW, tileH, cfg.use_nis ? 32 : 16, cfg.use_nis ? 24 : 16, map, p.maskLists, p.form);
-        }
-    }
+    if (p.tileLists) tile_lists(p, p.hiddenArea ? hidden_maps(p, *hidden) : HiddenMaps{});
     *plan = std::move(p);
     return Refusal{};
 }

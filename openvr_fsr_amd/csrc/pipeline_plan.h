@@ -42,6 +42,17 @@ struct Refusal {
 // (tests/test_pipeline_plan.py holds the same list); the library does not call it.
 const Refusal *plan_refusals(size_t *count);
 
+// The tiles a launch's workgroups walk and the mask groups the radius is tested on, for one output size.  EASU, RCAS, the fused kernel and
+// NVSharpen: 32x32 tiles (EASU: four of the 16x16 groups the reference dispatches); NVScaler: one workgroup per 32x24 mask group.  Everything
+// that counts, lists or launches tiles reads this -- tile_lists, hidden_tiles' caller, the launch arguments, ovrfsr_hidden_area_stats.
+struct TileGrid {
+    uint32_t tileW = 0, tileH = 0;
+    uint32_t groupW = 0, groupH = 0;
+    uint32_t tx = 0, ty = 0;     // tiles per row, tile rows
+    uint32_t tiles() const { return tx * ty; }
+};
+TileGrid tile_grid(bool useNis, bool doUpscale, uint32_t outW, uint32_t outH);
+
 struct Plan {
     // what was planned for: the canonical submitted format (a multisampled encoding included), its size, one eye per texture or both
     uint32_t inputWidth = 0, inputHeight = 0, inputFormat = 0;
@@ -81,18 +92,21 @@ struct Plan {
     std::vector<BilinTap> taps;
     uint32_t tapYOff = 0;
     uint32_t outsideCols = 0, outsideRows[2] = {0, 0}; // bilinear footprint bound of a 32-wide tile; rows for 32- and 24-row tiles
-    // mask-sorted tile lists, per eye: inside | ring | outside (ring: outside tiles 4-adjacent to an inside tile); one 4-dword record per
-    // list entry (OutsideArgs::tileRec); RCAS segments of the inside runs, 2 dwords each (RcasArgs::spanRec)
+    // the tile grid of the output: what the launches' tilesX / tilesY are, what the lists below index
+    TileGrid grid;
+    // the tile lists, per eye: Plan::lists holds inside | ring | outside (| rcas) -- the ring tiles follow the inside tiles so that ONE EASU
+    // launch over nInside + nRing entries also writes the intermediate of the ring, while RCAS walks the inside tiles only (ring: tiles
+    // 4-adjacent to a tile RCAS processes whose intermediate no other launch writes); one 4-dword record per list entry
+    // (OutsideArgs::tileRec); RCAS segments of the runs RCAS walks, 2 dwords each (RcasArgs::spanRec)
     std::vector<uint32_t> lists, recs, spans; // (PostProcessor frees these three once they are uploaded; the counts and offsets stay)
     uint32_t nInside[2] = {0, 0}, nOutside[2] = {0, 0}, nRing[2] = {0, 0}, nSpans[2] = {0, 0};
     size_t listOffInside[2] = {0, 0}, listOffOutside[2] = {0, 0}, listOffRing[2] = {0, 0}, spanOff[2] = {0, 0}; // spanOff in segments
-    bool listsShared = false;    // both eyes have identical lists
-    // hiddenArea: tiles per image, and how many of them no launch touches (hidden tiles; a skipped tile is always a hidden one).  In the
-    // two-kernel forms a hidden tile 4-adjacent to a tile RCAS processes stays in the ring segment -- EASU writes the intermediate texels
-    // RCAS's cross taps read -- and has no outside entry and no span.  Two-pass: RCAS walks a list of its own (every tile that is not
-    // hidden, inside | outside merged in raster order), and the spans are cut from that list
-    uint32_t nTiles = 0, nSkipped[2] = {0, 0}, nRcas[2] = {0, 0};
+    // what RCAS walks: the inside segment itself, or (two-pass under a hidden-area mesh) a fourth segment of its own -- every tile that is
+    // not hidden, inside | outside merged in raster order -- and the spans are cut from it
+    uint32_t nRcas[2] = {0, 0};
     size_t listOffRcas[2] = {0, 0};
+    uint32_t nSkipped[2] = {0, 0}; // hiddenArea: tiles no launch writes the destination of (a hidden ring tile is still a skipped one)
+    bool listsShared = false;    // both eyes have identical lists
 };
 
 // ovrfsr_set_hidden_area's meshes as the planner takes them: per eye, `triangles` triangles of 3 x (u, v) floats (header: the rule)

@@ -116,8 +116,9 @@ private:
         template <class Args> void Select(Args &a) const; // narrows an argument block of the whole batch (its view, its mask) to this pass
     };
     int EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const;
-    // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text
-    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, const char *what, Body body);
+    // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text.
+    // `mayOverlap` = false: no fork -- aux is the caller's stream, and no event is recorded or waited on
+    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, bool mayOverlap, const char *what, Body body);
     // one pass's two launches: `inside` with the list of the tiles touching the radius (+ `ring` tiles behind them) on the caller's stream,
     // then `outside` with the list and records of the other tiles on the auxiliary one
     template <class In, class Out, class LaunchIn, class LaunchOut>
@@ -125,8 +126,9 @@ private:
     const uint32_t *InsideList(int eye) const { return tileListDev_ + plan_.listOffInside[eye]; }
     const uint32_t *OutsideList(int eye) const { return tileListDev_ + plan_.listOffOutside[eye]; }
     const uint32_t *OutsideRecords(int eye) const { return tileRecDev_ + 4 * plan_.listOffOutside[eye]; }
-    const uint32_t *RcasList(int eye) const { return tileListDev_ + plan_.listOffRcas[eye]; } // (two-pass under a hidden-area mesh)
+    const uint32_t *RcasList(int eye) const { return tileListDev_ + plan_.listOffRcas[eye]; } // (the inside list, or RCAS's own: Plan::nRcas)
     const uint32_t *SpanRecords(int eye) const { return spanRecDev_ + 2 * plan_.spanOff[eye]; }
+    void RcasOverList(RcasArgs &a, int eye) const; // RCAS on the tiles the plan lists for it (Plan::nRcas), by span records where it has them
     int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
     template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
     void FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;

@@ -5,12 +5,13 @@
 //   hidden_probe CASES           one JSON line per line of the file CASES: the case line of tests/debug/plan_probe.cpp, followed by
 //       trianglesLeft trianglesRight and then 6 floats (u v u v u v) per triangle, the left mesh first
 //   Each line reports
-//     "no_mesh_equal"   the plan of the six-argument call and the plan of the call with an EMPTY mesh, serialised field by field, are equal
+//     "no_mesh_equal"   the plan of the six-argument call and the plan of the call with an EMPTY mesh, serialised by value (plan_serial.h), are equal
 //     "form", "form_plain"   the form with the mesh and of the six-argument call
 //     "tile_lists", "hidden_area", "lists_shared", "tiles", "tile" [w, h], "skipped" [l, r]
 //     "inside", "ring", "outside", "rcas"   per eye, the tile indices of each list segment as the plan holds them
 //     "spans"           per eye, [x0, tileRow, xEnd] of every RCAS segment
 //     "hidden"          per eye, the tile map the rule gives for the planned output size (hidden_tiles), row-major
+//     "digest"          the FNV-1a digest of the plan with the mesh, serialised by value (plan_serial.h)
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -18,37 +19,9 @@
 #include <string>
 #include <vector>
 #include "../../openvr_fsr_amd/csrc/pipeline_plan.h"
+#include "plan_serial.h"
 
 using namespace ovrfsr;
-
-template <class T>
-static void put(std::string &s, const T *v, size_t n)
-{
-    s.append(reinterpret_cast<const char *>(v), n * sizeof(T));
-    s += '|';
-}
-template <class T> static void put(std::string &s, const T &v) { put(s, &v, 1); }
-
-// every field of a Plan, in declaration order
-static std::string serialised(const Plan &p)
-{
-    std::string s;
-    put(s, p.inputWidth); put(s, p.inputHeight); put(s, p.inputFormat); put(s, p.onlyOneEye); put(s, p.outputWidth); put(s, p.outputHeight);
-    put(s, p.doUpscale); put(s, p.doSharpen); put(s, p.useNis); put(s, (int)p.form); put(s, p.tileLists); put(s, p.maskLists); put(s, p.hiddenArea);
-    put(s, p.overlapOutside); put(s, p.pipelineFormat); put(s, p.intermediateFormat); put(s, p.ownedFormat); put(s, p.launchPrec); put(s, p.rcasPrec);
-    put(s, p.easuCon, 16); put(s, p.rcasCon, 4);
-    put(s, reinterpret_cast<const unsigned char *>(&p.nis), sizeof p.nis);
-    put(s, &p.centre[0][0], 8); put(s, p.radius, 4); put(s, p.maskMode, 2); put(s, p.tieHalfMin); put(s, p.unorm8StoreGuard);
-    put(s, p.cellsW); put(s, p.cellsH); put(s, p.fusedCellsW); put(s, p.fusedCellsH); put(s, p.nisCellsW); put(s, p.nisCellsH);
-    put(s, p.rcpOut, 2); put(s, p.rcpExact);
-    for (const BilinTap &t : p.taps) { put(s, t.i0); put(s, t.frac); }
-    put(s, p.tapYOff); put(s, p.outsideCols); put(s, p.outsideRows, 2);
-    put(s, p.lists.data(), p.lists.size()); put(s, p.recs.data(), p.recs.size()); put(s, p.spans.data(), p.spans.size());
-    put(s, p.nInside, 2); put(s, p.nOutside, 2); put(s, p.nRing, 2); put(s, p.nSpans, 2);
-    put(s, p.listOffInside, 2); put(s, p.listOffOutside, 2); put(s, p.listOffRing, 2); put(s, p.spanOff, 2);
-    put(s, p.listsShared); put(s, p.nSkipped, 2);
-    return s;
-}
 
 static void print_list(const char *name, const Plan &p, const size_t off[2], const uint32_t n[2])
 {
@@ -76,16 +49,13 @@ int main(int argc, char **argv)
     while (std::getline(f, line)) {
         if (line.empty()) continue;
         std::istringstream in(line);
-        std::string id;
-        uint32_t format, w, h, count[2];
-        int oneEye;
-        long dest;
-        ovrfsr_config c;
-        std::memset(&c, 0, sizeof c);
-        c.struct_size = sizeof c;
-        in >> id >> format >> w >> h >> oneEye >> dest >> c.fsr_enabled >> c.use_nis >> c.debug_mode >> c.render_scale >> c.sharpness >> c.radius >>
-            c.proj_centre[0] >> c.proj_centre[1] >> c.proj_centre[2] >> c.proj_centre[3] >> c.out_width >> c.out_height >> c.precision >>
-            c.quantize_intermediate >> c.fused >> c.stage_mask >> c.pair_submit >> c.reference_formats >> count[0] >> count[1];
+        plan_serial::Case k;
+        uint32_t count[2] = {0, 0};
+        plan_serial::parse_case(in, k);
+        in >> count[0] >> count[1];
+        const ovrfsr_config &c = k.cfg;
+        const uint32_t format = k.format, w = k.width, h = k.height;
+        const int oneEye = k.oneEye;
         std::vector<float> uv[2];
         for (int eye = 0; eye < 2 && in; ++eye) {
             uv[eye].resize(6 * (size_t)count[eye]);
@@ -102,11 +72,16 @@ int main(int argc, char **argv)
         const Refusal r0 = plan_pipeline(c, format, w, h, oneEye != 0, &plain);
         const Refusal r1 = plan_pipeline(c, format, w, h, oneEye != 0, &empty, &none);
         const Refusal r = plan_pipeline(c, format, w, h, oneEye != 0, &p, &mesh);
-        std::printf("{\"id\": \"%s\", \"status\": %d, \"no_mesh_equal\": %d", id.c_str(), r.status,
-                    (int)(r0.status == r1.status && r0.status == r.status && serialised(plain) == serialised(empty)));
+        std::printf("{\"id\": \"%s\", \"status\": %d, \"no_mesh_equal\": %d", k.id.c_str(), r.status,
+                    (int)(r0.status == r1.status && r0.status == r.status && plan_serial::serialise(plain) == plan_serial::serialise(empty)));
         if (!r) {
-            const uint32_t tw = 32, th = p.useNis && p.doUpscale ? 24 : 32;
+            // the tile size is the plan's; the counts are recomputed from the output size, so that the grid does not vouch for itself
+            const uint32_t tw = p.grid.tileW, th = p.grid.tileH;
             const uint32_t tx = (p.outputWidth + tw - 1) / tw, ty = (p.outputHeight + th - 1) / th;
+            if (p.grid.tx != tx || p.grid.ty != ty) {
+                std::fprintf(stderr, "%s: the grid counts %u x %u tiles, the output size gives %u x %u\n", k.id.c_str(), p.grid.tx, p.grid.ty, tx, ty);
+                return 3;
+            }
             std::printf(", \"form\": \"%s\", \"form_plain\": \"%s\", \"out\": [%u, %u], \"tile_lists\": %d, \"hidden_area\": %d, \"lists_shared\": %d, "
                         "\"tiles\": %u, \"tile\": [%u, %u], \"skipped\": [%u, %u]", form_name(p.form), form_name(plain.form), p.outputWidth, p.outputHeight,
                         (int)p.tileLists, (int)p.hiddenArea, (int)p.listsShared, tx * ty, tw, th, p.nSkipped[0], p.nSkipped[1]);
@@ -132,7 +107,7 @@ int main(int argc, char **argv)
                 for (size_t i = 0; i < map.size(); ++i) std::printf("%s%u", i ? ", " : "", map[i]);
                 std::printf("]");
             }
-            std::printf("]");
+            std::printf("], \"digest\": \"%s\"", plan_serial::digest(p).c_str());
         }
         std::printf("}\n");
     }

@@ -3,11 +3,11 @@
 //
 //   plan_probe --refusals        one line per refusal the planner can produce: <status>\t<text>
 //   plan_probe CASES             one JSON line per line of the file CASES:
-//       id format width height onlyOneEye destFormat(-1: ctx-owned) fsr_enabled use_nis debug_mode render_scale sharpness radius
-//       proj_centre[4] out_width out_height precision quantize_intermediate fused stage_mask pair_submit reference_formats
+//       the 25 fields tests/debug/plan_serial.h names (plan_serial::Case)
 //   Each line reports the refusal or the plan (form, formats, stage selection, list sizes), the destination refusal and resolve_in_staging
 //   for the destination, "unorm8_guard" (is the guard of an EASU launch from the pipeline format into RGBA8 switched on: easu_tie_half_min),
-//   and "invariants": "ok" or the first structural invariant of the plan's tables that does not hold.
+//   "invariants": "ok" or the first structural invariant of the plan's tables that does not hold, and "digest": the FNV-1a digest of the
+//   whole plan serialised by value (plan_serial.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../openvr_fsr_amd/csrc/pipeline_plan.h"
+#include "plan_serial.h"
 
 using namespace ovrfsr;
 
@@ -30,7 +31,7 @@ static std::string fail(const char *fmt, long a = 0, long b = 0, long c = 0)
 }
 
 // the structural invariants of the tables a Plan holds; "ok" or the first that does not hold
-static std::string invariants(const Plan &p, bool nis)
+static std::string invariants(const Plan &p)
 {
     const uint32_t outW = p.outputWidth, outH = p.outputHeight;
     if (p.doUpscale) {
@@ -47,8 +48,10 @@ static std::string invariants(const Plan &p, bool nis)
         if (!p.lists.empty() || !p.recs.empty() || !p.spans.empty()) return "tables without tile lists";
         return "ok";
     }
-    const uint32_t tileW = 32, tileH = nis ? 24 : 32;
+    // the tile size is the plan's; the counts are recomputed from the output size here, so that a wrong grid cannot vouch for itself
+    const uint32_t tileW = p.grid.tileW, tileH = p.grid.tileH;
     const uint32_t tx = (outW + tileW - 1) / tileW, ty = (outH + tileH - 1) / tileH, nt = tx * ty;
+    if (p.grid.tx != tx || p.grid.ty != ty) return fail("the grid counts %ld x %ld tiles, the output size gives %ld columns", p.grid.tx, p.grid.ty, tx);
     if (p.recs.size() != 4 * p.lists.size()) return "one record per list entry";
     std::vector<uint8_t> seen(nt);
     for (int eye = 0; eye < 2; ++eye) {
@@ -87,7 +90,7 @@ static std::string invariants(const Plan &p, bool nis)
         }
     }
     // records: tile origin, footprint origin taps in range, extent within the planes the kernels allocate
-    const uint32_t rowsCap = p.outsideRows[nis ? 1 : 0];
+    const uint32_t rowsCap = p.outsideRows[p.useNis ? 1 : 0];
     for (size_t i = 0; i < p.lists.size(); ++i) {
         const uint32_t t = p.lists[i], ox0 = (t % tx) * tileW, oy0 = (t / tx) * tileH;
         const uint32_t r0 = p.recs[4 * i], r1 = p.recs[4 * i + 1], r2 = p.recs[4 * i + 2];
@@ -131,34 +134,26 @@ int main(int argc, char **argv)
     while (std::getline(f, line)) {
         if (line.empty()) continue;
         std::istringstream in(line);
-        std::string id;
-        uint32_t format, w, h;
-        int oneEye;
-        long dest;
-        ovrfsr_config c;
-        std::memset(&c, 0, sizeof c);
-        c.struct_size = sizeof c;
-        in >> id >> format >> w >> h >> oneEye >> dest >> c.fsr_enabled >> c.use_nis >> c.debug_mode >> c.render_scale >> c.sharpness >> c.radius >>
-            c.proj_centre[0] >> c.proj_centre[1] >> c.proj_centre[2] >> c.proj_centre[3] >> c.out_width >> c.out_height >> c.precision >>
-            c.quantize_intermediate >> c.fused >> c.stage_mask >> c.pair_submit >> c.reference_formats;
-        if (!in) {
+        plan_serial::Case k;
+        if (!plan_serial::parse_case(in, k)) {
             std::fprintf(stderr, "malformed case line: %s\n", line.c_str());
             return 2;
         }
+        const ovrfsr_config &c = k.cfg;
         Plan p;
-        const Refusal r = plan_pipeline(c, format, w, h, oneEye != 0, &p);
-        std::printf("{\"id\": %s, \"status\": %d, \"text\": %s", quoted(id.c_str()).c_str(), r.status, quoted(r.text).c_str());
+        const Refusal r = plan_pipeline(c, k.format, k.width, k.height, k.oneEye != 0, &p);
+        std::printf("{\"id\": %s, \"status\": %d, \"text\": %s", quoted(k.id.c_str()).c_str(), r.status, quoted(r.text).c_str());
         if (!r) {
-            const uint32_t d = dest < 0 ? p.ownedFormat : (uint32_t)dest;
+            const uint32_t d = k.dest < 0 ? p.ownedFormat : (uint32_t)k.dest;
             const Refusal dr = destination_refusal(p, d);
             std::printf(", \"form\": %s, \"out\": [%u, %u], \"upscale\": %d, \"sharpen\": %d, \"pipeline\": %u, \"mid\": %u, \"owned\": %u, \"tile_lists\": %d, "
                         "\"overlap\": %d, \"lists_shared\": %d, \"dest_status\": %d, \"dest_text\": %s, \"dest_disables\": %d, \"resolve_in_staging\": %d, "
-                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"unorm8_guard\": %d, \"invariants\": %s",
+                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"unorm8_guard\": %d, \"invariants\": %s, \"digest\": \"%s\"",
                         quoted(form_name(p.form)).c_str(), p.outputWidth, p.outputHeight, (int)p.doUpscale, (int)p.doSharpen, p.pipelineFormat,
                         p.intermediateFormat, p.ownedFormat, (int)p.tileLists, (int)p.overlapOutside, (int)p.listsShared, dr.status, quoted(dr.text).c_str(),
                         (int)dr.disables, (int)resolve_in_staging(p, d), p.nInside[0], p.nInside[1], p.nRing[0], p.nRing[1], p.nOutside[0], p.nOutside[1],
                         p.nSpans[0], p.nSpans[1], (int)std::isfinite(easu_tie_half_min(p, p.pipelineFormat, OVRFSR_FORMAT_RGBA8_UNORM, INFINITY)),
-                        quoted(invariants(p, c.use_nis != 0).c_str()).c_str());
+                        quoted(invariants(p).c_str()).c_str(), plan_serial::digest(p).c_str());
         }
         std::printf("}\n");
     }

@@ -1,7 +1,8 @@
 """The hidden-area mesh without a GPU (include/openvr_fsr_amd.h, "hidden-area mesh"): (a) the classification rule, ovrfsr_hidden_tiles through
 the built library against a numpy brute-force restatement (tests/hidden_ref.py) and known answers; (b) the planner under a mesh,
 tests/debug/hidden_probe.cpp linked from the planner's three sources under AddressSanitizer and UBSan as a stand-alone program: list
-structure, spans, RCAS neighbours, the plan without a mesh unchanged, the form unchanged; (c) the C boundary: symbols and refusals."""
+structure, spans, RCAS neighbours, the plan without a mesh unchanged, the form unchanged, and every plan's digest the one recorded before the
+tile lists were built in steps (tests/golden/plan_digests_parent.json); (c) the C boundary: symbols and refusals."""
 import ctypes as C
 import shutil
 
@@ -116,15 +117,26 @@ def test_the_test_meshes_hide_something_everywhere():
 # ---- (b) the planner -----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def probe():
-    run = R.build_probe()
+    """the probe; every line it plans is compared with the recorded digest of the parent commit's plan (ids unique per call)"""
+    build = R.build_probe()
+
+    def run(lines):
+        plans = build(lines)
+        TP.assert_parent_digests("hidden_probe", plans)
+        return plans
+
     yield run
-    shutil.rmtree(run.tmp, ignore_errors=True)
+    shutil.rmtree(build.tmp, ignore_errors=True)
+
+
+def _no_mesh_lines():
+    return [R.with_mesh(line) for _, line, _ in TP.FORM_TABLE]
 
 
 def test_plan_without_a_mesh_is_unchanged(probe):
     """every row of test_pipeline_plan.FORM_TABLE: the six-argument call and the call with an empty mesh give the same plan, field by field
     (lists, records, spans, taps and form included), and the same refusal"""
-    got = probe([R.with_mesh(line) for _, line, _ in TP.FORM_TABLE])
+    got = probe(_no_mesh_lines())
     for (name, _, want), g in zip(TP.FORM_TABLE, got):
         assert g["no_mesh_equal"] == 1, name
         assert g["status"] == want.get("status", 0), name
@@ -156,14 +168,34 @@ PLAN_FORMS = [
 ]
 
 
-def _plan_line(name, fmt, one_eye, shape, cfg):
+def _plan_line(name, fmt, one_eye, shape, cfg, mesh="mesh"):
+    """(the id names form, shape and mesh: unique over this file, as the digest record needs it)"""
     iw, ih, ow, oh = shape
-    return TP._line(name, fmt, iw, ih, one_eye, -1, fsr_enabled=1, out_width=ow, out_height=oh, sharpness=0.9, **cfg)
+    return TP._line("%s/%dx%d-%dx%d/%s" % ((name,) + tuple(shape) + (mesh,)), fmt, iw, ih, one_eye, -1, fsr_enabled=1, out_width=ow, out_height=oh,
+                    sharpness=0.9, **cfg)
+
+
+# the lines the tests below plan, each behind a name: test_digest_record_names_these_lines reads the same functions
+def _mesh_lines(shape):
+    return [R.with_mesh(_plan_line(n, f, one, shape, cfg), R.MESH[0], R.MESH[1]) for n, f, one, cfg, _, _ in PLAN_FORMS]
+
+
+def _shared_or_not_lines():
+    line, other = (_plan_line("shared-or-not", TP.RGBA8, 1, PLAN_SHAPES[0], dict(radius=2.0), mesh) for mesh in ("same", "different"))
+    return [R.with_mesh(line, R.MESH[0], R.MESH[0]), R.with_mesh(other, R.MESH[0], R.MESH[1])]
+
+
+def _everything_lines():
+    return [R.with_mesh(_plan_line(n, f, one, PLAN_SHAPES[1], cfg, "everything"), R.EVERYTHING, R.EVERYTHING) for n, f, one, cfg, skips, _ in PLAN_FORMS if skips]
+
+
+def _left_only_lines():
+    return [R.with_mesh(_plan_line("left-only", TP.RGBA8, 1, PLAN_SHAPES[0], dict(M), "left"), R.MESH[0], None)]
 
 
 @pytest.mark.parametrize("shape", PLAN_SHAPES, ids=["%dx%d-%dx%d" % s for s in PLAN_SHAPES])
 def test_lists_under_a_mesh(probe, shape):
-    lines = [R.with_mesh(_plan_line(n, f, one, shape, cfg), R.MESH[0], R.MESH[1]) for n, f, one, cfg, _, _ in PLAN_FORMS]
+    lines = _mesh_lines(shape)
     ow, oh = shape[2:]
     for (name, _, one, cfg, skips, two_kernel), p in zip(PLAN_FORMS, probe(lines)):
         assert p["status"] == 0 and p["form"] == p["form_plain"], (name, p["form"], p["form_plain"])   # the mesh never changes the form
@@ -222,14 +254,12 @@ def test_lists_under_a_mesh(probe, shape):
 
 def test_lists_shared_compares_the_final_lists(probe):
     """unmasked, one eye per texture: equal meshes give shared lists, different meshes do not"""
-    line = _plan_line("shared-or-not", TP.RGBA8, 1, PLAN_SHAPES[0], dict(radius=2.0))
-    same, different = probe([R.with_mesh(line, R.MESH[0], R.MESH[0]), R.with_mesh(line, R.MESH[0], R.MESH[1])])
+    same, different = probe(_shared_or_not_lines())
     assert same["lists_shared"] == 1 and different["lists_shared"] == 0
 
 
 def test_everything_hidden_plans_no_launch(probe):
-    lines = [R.with_mesh(_plan_line(n, f, one, PLAN_SHAPES[1], cfg), R.EVERYTHING, R.EVERYTHING) for n, f, one, cfg, skips, _ in PLAN_FORMS if skips]
-    for p in probe(lines):
+    for p in probe(_everything_lines()):
         assert p["status"] == 0 and p["form"] == p["form_plain"], p["id"]
         for eye in (0, 1):
             assert p["skipped"][eye] == p["tiles"], p["id"]
@@ -238,9 +268,17 @@ def test_everything_hidden_plans_no_launch(probe):
 
 def test_one_eye_without_a_mesh(probe):
     """a mesh for the left eye only: the right eye's lists hold every tile"""
-    p = probe([R.with_mesh(_plan_line("left-only", TP.RGBA8, 1, PLAN_SHAPES[0], dict(M)), R.MESH[0], None)])[0]
+    p = probe(_left_only_lines())[0]
     assert p["hidden_area"] == 1 and p["skipped"][0] > 0 and p["skipped"][1] == 0
     assert len(p["inside"][1]) + len(p["outside"][1]) == p["tiles"]
+
+
+def test_digest_record_names_these_lines():
+    """the ids of the lines planned above are unique over the file, and the record holds no hidden_probe id that none of them has"""
+    lines = _no_mesh_lines() + [line for shape in PLAN_SHAPES for line in _mesh_lines(shape)] + _shared_or_not_lines() + _everything_lines() + _left_only_lines()
+    ids = [line.split(" ", 1)[0] for line in lines]
+    assert len(set(ids)) == len(ids), sorted(i for i in set(ids) if ids.count(i) > 1)
+    assert set(TP.parent_digests("hidden_probe")) <= set(ids)
 
 
 # ---- (c) the C boundary ----------------------------------------------------------------------------------------------------------------

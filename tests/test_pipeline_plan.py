@@ -3,7 +3,8 @@ two host constant units (constants.cpp, nis_config.cpp) -- nothing from the kern
 as a child process.  Checked: (a) a hand-written table of the forms of configurations the project names elsewhere, (b) every refusal the planner
 can produce is reached by the launch-form matrix (tools/debug/record_forms.py), (c) structural invariants of the tile, span, record and tap
 tables at shapes from 1x1 to 16384^2, (d) status, text and owned format agree, case by case, with what the library at the commit before
-the planner did on an MI355X (tests/golden/launch_forms_parent.json)."""
+the planner did on an MI355X (tests/golden/launch_forms_parent.json), (e) every plan of (a)-(c), serialised by value (tests/debug/plan_serial.h),
+has the digest it had before the tile lists were built in steps (tests/golden/plan_digests_parent.json)."""
 import functools
 import importlib.util
 import json
@@ -75,6 +76,32 @@ def _plan(probe, lines):
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def parent_digests(probe_name):
+    """id -> digest of the plan at the recorded parent commit, for the lines one probe plans"""
+    with open(os.path.join(ROOT, "tests", "golden", "plan_digests_parent.json")) as f:
+        return json.load(f)[probe_name]
+
+
+def assert_parent_digests(probe_name, plans):
+    """every planned line has its recorded digest -- an id without a record fails -- and a refused line has none"""
+    record = parent_digests(probe_name)
+    ids = [p["id"] for p in plans]
+    assert len(set(ids)) == len(ids), sorted(i for i in set(ids) if ids.count(i) > 1)
+    for p in plans:
+        if p["status"] == 0:
+            assert p["id"] in record, p["id"]
+            assert p["digest"] == record[p["id"]], p["id"]
+        else:
+            assert p["id"] not in record, p["id"]
+
+
+def _plan_checked(probe, lines):
+    plans = _plan(probe, lines)
+    assert_parent_digests("plan_probe", plans)
+    return plans
+
+
 # ---- (a) the forms of configurations the project names --------------------------------------------------------------------------
 def _named(name, fmt, shape, want, dest=-1, **cfg):
     iw, ih, ow, oh = shape
@@ -127,8 +154,12 @@ FORM_TABLE = [
 ]
 
 
+def _form_lines():
+    return [line for _, line, _ in FORM_TABLE]
+
+
 def test_form_table(probe):
-    got = _plan(probe, [line for _, line, _ in FORM_TABLE])
+    got = _plan_checked(probe, _form_lines())
     for (name, _, want), g in zip(FORM_TABLE, got):
         want = dict(want)
         want.setdefault("status", 0)
@@ -140,8 +171,7 @@ def test_form_table(probe):
 DEST = {"owned": -1, "rgba8": RGBA8, "rgba16f": RGBA16F, "rgba32f": RGBA32F, "rgb10a2": RGB10A2, "bgra8": BGRA8}
 
 
-@pytest.fixture(scope="module")
-def matrix_plans(probe):
+def _matrix_lines():
     R = _matrix()
     cases = R.cases()
     lines = []
@@ -149,7 +179,13 @@ def matrix_plans(probe):
         iw, ih, _, _ = c["shape"]
         cfg = dict(c["cfg"], pair_submit=1 if c["kind"] == "pair" else 0)
         lines.append(_line(c["id"], R.SOURCES[c["src"]], iw, ih, c["kind"] != "shared", DEST[c["dst"]], **cfg))
-    return cases, _plan(probe, lines)
+    return cases, lines
+
+
+@pytest.fixture(scope="module")
+def matrix_plans(probe):
+    cases, lines = _matrix_lines()
+    return cases, _plan_checked(probe, lines)
 
 
 # every refusal of the planner's table, in its order.  The two marked unreachable are defensive: the matrix cannot produce them, because no
@@ -271,7 +307,7 @@ VARIANTS = [("easu-rcas", RGBA8, 1, {}), ("easu-rcas-shared", RGBA8, 0, {}), ("e
 @pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d-%dx%d" % s for s in SHAPES])
 def test_table_invariants(probe, shape):
     lines = _invariant_lines(shape, VARIANTS)
-    plans = _plan(probe, lines)
+    plans = _plan_checked(probe, lines)
     planned = [p for p in plans if p["status"] == 0]
     assert planned, plans   # (NIS refuses 128x96 -> 96x72 and the fused kernel does not fit there: the other variants plan)
     for p in planned:
@@ -286,12 +322,24 @@ def test_table_invariants(probe, shape):
         assert any(p["tile_lists"] for p in planned), shape
 
 
+def _largest_lines():
+    return _invariant_lines(LARGEST, VARIANTS[:1])[:1]
+
+
 def test_table_invariants_largest_output(probe):
     """12288^2 -> 16384^2: 512 x 512 tiles per eye; tile lists only (the masked EASU+RCAS form)"""
-    plans = _plan(probe, _invariant_lines(LARGEST, VARIANTS[:1])[:1])
+    plans = _plan_checked(probe, _largest_lines())
     p = plans[0]
     assert p["status"] == 0 and p["form"] == "mask-sorted" and p["invariants"] == "ok", p
     assert p["inside"][0] + p["outside"][0] == 512 * 512 and p["spans"][0] > 0, p
+
+
+def test_digest_record_names_these_lines():
+    """the ids of (a)-(c), from the functions the tests above plan from, are unique, and the record holds no plan_probe id that none of them has"""
+    lines = _form_lines() + _matrix_lines()[1] + [line for shape in SHAPES for line in _invariant_lines(shape, VARIANTS)] + _largest_lines()
+    ids = [line.split(" ", 1)[0] for line in lines]
+    assert len(set(ids)) == len(ids), sorted(i for i in set(ids) if ids.count(i) > 1)
+    assert set(parent_digests("plan_probe")) <= set(ids)
 
 
 # ---- machine code unmoved -----------------------------------------------------------------------------------------------------------
