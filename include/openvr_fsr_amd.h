@@ -386,7 +386,8 @@ OVRFSR_API int ovrfsr_pair_pending(const ovrfsr_ctx *ctx);
  *   - a skipped tile is always a hidden tile.  Which hidden tiles are skipped is the plan's choice per form, reported by
  *     ovrfsr_hidden_area_stats: every hidden tile wherever the plan walks tile lists -- product arithmetic (OVRFSR_PRECISION_FP32 and
  *     FP32_EXACT) with an upscale stage: EASU-only, two-pass, mask-sorted, fused, fused with outside tiles, NVScaler --, none in the
- *     strict build and in the sharpen-only forms (RCAS or NVSharpen alone).  The front passes (multisample resolve, BGRA8 re-order,
+ *     strict build, in the sharpen-only forms (RCAS or NVSharpen alone) and for a float submission under OVRFSR_HDR_DOMAIN_SRTM (below: its
+ *     back pass walks whole images).  The front passes (multisample resolve, BGRA8 re-order,
  *     R11G11B10F unpack) run on the whole image.  (In the two-kernel forms EASU still writes the INTERMEDIATE of a hidden tile that
  *     shares an edge with a tile RCAS processes: RCAS's cross taps read it.  The destination is not written there.) */
 
@@ -404,6 +405,62 @@ OVRFSR_API int ovrfsr_hidden_area_stats(const ovrfsr_ctx *ctx, int eye, uint32_t
  * tile, else 0.  hidden_len: bytes at `hidden`; too few (or any bad argument, checked as above): OVRFSR_ERR_INVALID_ARGUMENT, nothing written. */
 OVRFSR_API int ovrfsr_hidden_tiles(const float *uv, uint32_t triangle_count, uint32_t out_w, uint32_t out_h,
                                    uint32_t tile_w, uint32_t tile_h, uint8_t *hidden, size_t hidden_len);
+
+/* ---- HDR domain: float eye images are tone-mapped around the filters ---------------------------------------
+ * ffx_fsr1.h states the input domain of EASU and RCAS as {0 to 1}: RCAS's limiter is built on a peak of 1.0 (it changes sign where a
+ * neighbourhood's maximum exceeds 1), and EASU's edge analysis follows the largest tap, so one specular highlight of a few hundred decides
+ * direction and length of the filter for every pixel around it.  The same header ships the answer, the Simple Reversible Tone-Mapper
+ * (FsrSrtmF / FsrSrtmInvF, src/fsr/ffx_fsr1.h:1029-1046): linear HDR to {0 to 1} in front of the filters and back behind them, RGB ratios
+ * preserved.  DEPARTURE FROM THE REFERENCE, opt-in: the reference filters linear HDR as it comes (and so does OVRFSR_HDR_DOMAIN_LINEAR, the
+ * default: every byte is what it has always been).  No ABI change: a host probes for these symbols.
+ *
+ * The rule, in fp32, every operator rounded once as written, IEEE division, on the host (ovrfsr_hdr_map) and on the device alike:
+ *   forward   m = max(max(r, g), b);  k = 1.0f / (m + 1.0f);                         r *= k; g *= k; b *= k
+ *   back      m = max(max(r, g), b);  k = 1.0f / max(1.0f / 32768.0f, 1.0f - m);     r *= k; g *= k; b *= k
+ * Alpha is not touched.  Covered values: finite and >= 0 (no ordering question about max arises for them); negative, NaN and Inf texels
+ * fall under the texel-value clause above: outside the parity contract, inside the memory-safety one.  The round trip is NOT the
+ * identity: forward rounds, and the back mapping's divisor is clamped, so it peaks at 32768 times the mapped value -- a texel beyond 32767
+ * comes back as at most 32768, and a half destination (largest finite value 65504) holds whatever a mapped value <= 1 un-maps to.  The
+ * filters can overshoot 1 in the mapped domain, though: RCAS's limiter bounds the lobe from the four cross taps, not the result, and on
+ * noise between highlights the reference's own arithmetic (the CPU oracle) returns mapped values up to 2.6.  Such a value un-maps to 32768
+ * times itself, and from 2 upwards that is past the half range: an RGBA16F destination then holds +Inf there, as the store conversion of
+ * any value beyond 65504 does; an RGBA32F destination holds the finite product.
+ *
+ * The contract, with OVRFSR_HDR_DOMAIN_SRTM set and a submission whose pipeline format is float (RGBA16F, RGBA32F, R11G11B10F, single-sample
+ * or OVRFSR_FORMAT_MS) -- a composition, bit for bit:
+ *   1. the front pass runs where the submission needs one (multisample resolve, R11G11B10F unpack);
+ *   2. a forward pass writes a ctx-owned single-sample RGBA32F copy holding the mapped values;
+ *   3. the pipeline runs exactly as it is planned for an RGBA32F submission of that size with an RGBA32F destination -- form, intermediate,
+ *      mask, NIS or FSR, reference_formats are that plan's -- into a second ctx-owned RGBA32F image;
+ *   4. a back pass un-maps that image into the destination the call names, with that format's store conversion: RGBA32F as is, RGBA16F
+ *      rounded to nearest even, RGBA8 saturate, x 255, + 0.5, truncate.
+ * So the bytes equal: decode the submission to fp32, map, apply as an RGBA32F image into an RGBA32F `out` on a ctx without the setting,
+ * un-map, convert.  The two mapped copies are fp32 on purpose: near m -> 1 the back mapping multiplies by 1 / (1 - m), and a half there
+ * (spacing 2^-11) would turn a texel of 1000 into anything between 670 and 2000.
+ *   - The format of a ctx-owned output (out->data == NULL) stays what it is for that submission: RGBA16F for half and R11G11B10F, RGBA32F for
+ *     float, RGBA8 under cfg.reference_formats = 1.
+ *   - UNORM submissions (RGBA8, BGRA8, RGB10A2) ignore the setting entirely: plans, launches and bytes are what they are without it.
+ *   - Batches, shared side-by-side textures and pair_submit work like any other call; after the first call for a size nothing is allocated
+ *     and the call can be captured; the debug-mode timer brackets the two passes, as it brackets the resolve.
+ *   - A hidden-area mesh is IGNORED, as in the strict build and the sharpen-only forms: the back pass walks whole images, so nothing may be
+ *     left unwritten; ovrfsr_hidden_area_stats reports 0 skipped tiles.
+ *   - OVRFSR_PRECISION_FP32_EXACT: RCAS stores fp32 under this setting, no UNORM8 byte for exact stores to guard, so it runs as in
+ *     OVRFSR_PRECISION_FP32 (EASU's UNORM8 intermediate under reference_formats = 1 is the strict build's in either).  What the submission is
+ *     refused for without the setting it is refused for with it; nothing else is.  Where a submission plans and its RGBA32F twin would not
+ *     (an LDS footprint only the half kernels hold: steep minification), the setting is not applied to that plan.
+ * What it costs -- three more passes over 16-byte texels -- and what folding the mapping into the kernels' staging and stores would save:
+ * profiles/hdr_domain.txt. */
+#define OVRFSR_HDR_DOMAIN_LINEAR 0 /* the filters see the texel values as submitted: the default, and the reference's behaviour */
+#define OVRFSR_HDR_DOMAIN_SRTM 1   /* float submissions are filtered in FSR 1's reversible tone-mapped domain */
+/* OVRFSR_ERR_INVALID_ARGUMENT -- the stored value is left as it was -- for a NULL ctx or a value other than the two above.  Like
+ * ovrfsr_set_hidden_area it drops a recorded pair_submit eye, re-enables a disabled ctx and makes the next apply rebuild (refused under stream
+ * capture, as any build is).  The call itself touches no device resource -- what it retires is released by that next apply -- so it is
+ * accepted while a stream is being captured and leaves the capture valid.  ovrfsr_reset and ovrfsr_set_config keep the value. */
+OVRFSR_API int ovrfsr_set_hdr_domain(ovrfsr_ctx *ctx, int domain);
+OVRFSR_API int ovrfsr_get_hdr_domain(const ovrfsr_ctx *ctx, int *domain);
+/* Constants-only, no GPU: the mapping itself on n RGB triples (rgb_in and rgb_out: 3 * n floats; they may be the same array), forward
+ * (inverse = 0) or back (inverse = 1).  OVRFSR_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer with n > 0 or any other `inverse`. */
+OVRFSR_API int ovrfsr_hdr_map(const float *rgb_in, float *rgb_out, size_t n, int inverse);
 
 /* ---- constants-only entry points (known-answer tests; no GPU needed) ------------------------- */
 

@@ -20,6 +20,7 @@ def format_ms(fmt, samples):
 PRECISION_FP32, PRECISION_FP32_STRICT = 0, 2
 PRECISION_FP32_EXACT = 3  # FP32's arithmetic; every UNORM8 byte stored is the strict build's (header, ovrfsr_precision)
 EYE_LEFT, EYE_RIGHT = 0, 1
+HDR_DOMAIN_LINEAR, HDR_DOMAIN_SRTM = 0, 1  # ovrfsr_set_hdr_domain: float submissions filtered as submitted / in FSR 1's reversible tone-mapped domain
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "HIP", 4: "NO_DEVICE", 5: "DISABLED", 6: "OUT_OF_MEMORY"}
 
@@ -120,6 +121,10 @@ def library():
         L.ovrfsr_set_hidden_area.argtypes = [C.c_void_p, C.c_int, f32p, C.c_uint32]
         L.ovrfsr_hidden_area_stats.argtypes = [C.c_void_p, C.c_int, u32p, u32p]
         L.ovrfsr_hidden_tiles.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t]
+    if hasattr(L, "ovrfsr_set_hdr_domain"):  # (probed the same way)
+        L.ovrfsr_set_hdr_domain.argtypes = [C.c_void_p, C.c_int]
+        L.ovrfsr_get_hdr_domain.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.ovrfsr_hdr_map.argtypes = [f32p, f32p, C.c_size_t, C.c_int]
     if L.ovrfsr_abi_version() != 5:
         raise OvrFsrError(1, "ABI version mismatch")
     _LIB = L
@@ -186,6 +191,18 @@ def hidden_tiles(uv, outW, outH, tileW=32, tileH=32):
     if rc != 0:
         raise OvrFsrError(rc)
     return hidden
+
+
+def hdr_map(rgb, inverse=False):
+    """ovrfsr_hdr_map: the SRTM mapping (forward, or back with ``inverse``) on an array of RGB triples [..., 3]; float32, same shape (no GPU)."""
+    a = np.ascontiguousarray(rgb, np.float32)
+    if a.shape[-1:] != (3,):
+        raise ValueError("expected RGB triples [..., 3]")
+    out = np.empty_like(a)
+    rc = library().ovrfsr_hdr_map(a.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)), a.size // 3, int(bool(inverse)))
+    if rc != 0:
+        raise OvrFsrError(rc)
+    return out
 
 
 def config_from_json(text):

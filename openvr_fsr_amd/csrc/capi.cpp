@@ -9,6 +9,7 @@
 #include "postprocessor.hpp"
 #include "fsr_launch.h"
 #include "fsr_bounds.h"
+#include "hdr_map.h"
 #include "nis_tables.h"
 
 struct ovrfsr_ctx {
@@ -128,6 +129,31 @@ OVRFSR_API int ovrfsr_hidden_tiles(const float *uv, uint32_t triangle_count, uin
         ovrfsr::hidden_tiles(uv, triangle_count, nullptr, 0, false, out_w, out_h, tile_w, tile_h, hidden);
         return (int)OVRFSR_OK;
     });
+}
+
+// ---- HDR domain (header).  The argument checks live here, like the mesh's.
+OVRFSR_API int ovrfsr_set_hdr_domain(ovrfsr_ctx *ctx, int domain)
+{
+    if (!ctx || (domain != OVRFSR_HDR_DOMAIN_LINEAR && domain != OVRFSR_HDR_DOMAIN_SRTM)) return OVRFSR_ERR_INVALID_ARGUMENT; // the stored value stays
+    return guarded([&] { return ctx->pp->SetHdrDomain(domain); });
+}
+
+OVRFSR_API int ovrfsr_get_hdr_domain(const ovrfsr_ctx *ctx, int *domain)
+{
+    if (!ctx || !domain) return OVRFSR_ERR_INVALID_ARGUMENT;
+    *domain = ctx->pp->HdrDomain();
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_hdr_map(const float *rgb_in, float *rgb_out, size_t n, int inverse)
+{
+    if ((n && (!rgb_in || !rgb_out)) || (inverse != 0 && inverse != 1)) return OVRFSR_ERR_INVALID_ARGUMENT; // (nothing written)
+    for (size_t i = 0; i < n; ++i) {
+        float r = rgb_in[3 * i], g = rgb_in[3 * i + 1], b = rgb_in[3 * i + 2];
+        ovrfsr::hdr_map(r, g, b, inverse != 0);
+        rgb_out[3 * i] = r; rgb_out[3 * i + 1] = g; rgb_out[3 * i + 2] = b;
+    }
+    return OVRFSR_OK;
 }
 
 OVRFSR_API void ovrfsr_config_default(ovrfsr_config *cfg)

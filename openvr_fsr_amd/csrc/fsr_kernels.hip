@@ -513,6 +513,12 @@ hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t src
     return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
+} // namespace ovrfsr
+// The forward and back passes of OVRFSR_HDR_DOMAIN_SRTM with their launchers: a file of their own inside this unit (it opens its own
+// namespaces).  Here, in front of launch_rcas, so that the kernels launch_rcas instantiates stay the last ones of the code object.
+#include "fsr_hdr_domain.inc"
+namespace ovrfsr {
+
 #ifdef OVRFSR_BOUNDS
 // Drives the checked accessors through every kind of violation exactly once (tests/test_gpu_bounds.py asserts the counts): proof that a
 // zero from a campaign means "nothing out of bounds", not "nothing checked".  64 threads, 1024 bytes of dynamic LDS.

@@ -522,8 +522,9 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
     return OVRFSR_OK;
 }
 
-Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden)
+// the plan of one submission as it is filtered: what plan_pipeline has always been
+static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
+                             const HiddenArea *hidden)
 {
     Plan p;
     p.inputWidth = width; p.inputHeight = height; p.inputFormat = format;
@@ -644,6 +645,27 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
     return Refusal{};
 }
 
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
+                      const HiddenArea *hidden, int hdrDomain)
+{
+    const uint32_t pf = pipeline_format(format);
+    if (hdrDomain == OVRFSR_HDR_DOMAIN_SRTM && (pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F)) {
+        // FSR 1's reversible tone-mapped domain (header, "HDR domain"): the pipeline is the RGBA32F submission's, between a forward pass that
+        // writes its input and a back pass that reads its result, both ctx-owned RGBA32F images.  No mesh: the back pass walks whole images.
+        Plan p;
+        if (!plan_filtered(cfg, OVRFSR_FORMAT_RGBA32F, width, height, onlyOneEye, &p, nullptr)) {
+            p.hdrDomain = true;
+            p.inputFormat = format;                                                    // what the plan is FOR (PostProcessor::PlannedFor)
+            p.ownedFormat = cfg.reference_formats ? reference_output_format(pf) : pf;  // the submission's own rule
+            p.rcasPrec = p.launchPrec;                                                 // RCAS stores fp32 here: nothing for exact stores to guard
+            *plan = std::move(p);
+            return Refusal{};
+        }
+        // (refused as RGBA32F: whatever the submission itself gets -- the same refusal, or its own plan with the setting not applied)
+    }
+    return plan_filtered(cfg, format, width, height, onlyOneEye, plan, hidden);
+}
+
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat)
 {
     // exact stores: the sharpen stage's destination must be RGBA8 too (a BGRA8 destination is refused below in every mode)
@@ -707,6 +729,7 @@ static bool packed_in_staging(const Plan &plan, uint32_t destFormat)
 
 bool resolve_in_staging(const Plan &plan, uint32_t destFormat)
 {
+    if (plan.hdrDomain) return false; // the kernels read the forward pass's RGBA32F copy: the front pass, where one exists, feeds that pass
     if (packed_in_staging(plan, destFormat)) return true;
 #ifdef OVRFSR_MSAA_RESOLVE_PASS
     (void)plan; (void)destFormat;

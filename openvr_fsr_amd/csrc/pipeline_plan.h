@@ -68,6 +68,8 @@ struct Plan {
     bool hiddenArea = false;     // a hidden-area mesh is in effect (HiddenArea): hidden tiles are in no list but the ring; the strict build,
                                  // sharpen-only forms and anything without an upscale stage ignore the mesh
     bool overlapOutside = false; // ... and their outside-tile kernel runs on the ctx's auxiliary stream (see PostProcessor::Fork)
+    bool hdrDomain = false;      // OVRFSR_HDR_DOMAIN_SRTM is in effect (plan_pipeline, `hdrDomain`): everything here but inputFormat and
+                                 // ownedFormat is the plan of the RGBA32F submission; the forward and back passes run around it
     // pipeline: what the kernels see in the submission's place; intermediate: the upscale stage's destination in front of a sharpen stage;
     // owned: the textures the ctx creates for itself (cfg.reference_formats)
     uint32_t pipelineFormat = 0, intermediateFormat = 0, ownedFormat = 0;
@@ -125,8 +127,14 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
 
 // `format`: canonical (a single-sample encoding reduced to its base format).  On a refusal *plan is left as it was.
 // `hidden`: the ctx's hidden-area meshes, or null (none set): the plan is then what it has always been.
+// `hdrDomain`: ovrfsr_set_hdr_domain's value.  OVRFSR_HDR_DOMAIN_SRTM with a float pipeline format (RGBA16F, RGBA32F, R11G11B10F, any sample
+// count) plans the pipeline of the RGBA32F submission of that size into an RGBA32F destination -- form, intermediate, mask, tile lists --,
+// without the mesh (the back pass walks whole images), and RCAS in the launch precision (no UNORM8 byte leaves RCAS, so exact stores have
+// nothing to guard there).  Plan::inputFormat stays the submission's and Plan::ownedFormat follows the submission's own rule.  Where the
+// submission plans and its RGBA32F twin does not (a footprint only the half kernels' LDS planes hold), the setting is not applied.  UNORM
+// formats and OVRFSR_HDR_DOMAIN_LINEAR: the plan is what it has always been.
 Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden = nullptr);
+                      const HiddenArea *hidden = nullptr, int hdrDomain = OVRFSR_HDR_DOMAIN_LINEAR);
 
 // what depends on the destination the call names
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat);

@@ -154,8 +154,9 @@ void PostProcessor::ResetKeeping(bool keepRetired)
     sequence_.Reset(!keepRetired); // a recorded first eye of cfg.pair_submit is dropped (header); an explicit reset forgets the learned order too
     enabled_ = true;
     initialized_ = false;
+    replan_ = false;
     plan_ = Plan{};             // nothing of a previous configuration survives: the next apply plans afresh
-    for (DeviceBuffer *b : {&swizzled_, &resolved_, &upscaled_, &sharpened_}) b->release();
+    for (DeviceBuffer *b : {&swizzled_, &resolved_, &upscaled_, &sharpened_, &hdrIn_, &hdrOut_}) b->release();
     for (void *t : {(void *)nisCoefDev_, (void *)bilinDev_, (void *)tileListDev_})
         if (t) (void)hipFree(t);
     nisCoefDev_ = nullptr;
@@ -184,9 +185,22 @@ int PostProcessor::SetHiddenArea(int eye, const float *uv, uint32_t triangles)
     return OVRFSR_OK;
 }
 
+// ovrfsr_set_hdr_domain behind its argument check: the value, and what SetHiddenArea does -- a recorded pair_submit eye is dropped, a disabled
+// ctx is enabled again and the next apply plans afresh.  The device side of that reset waits for that apply (replan_, EnsurePlanned): a
+// setter has no stream to ask about a capture, and freeing device memory while one is under way would invalidate it.  So the call is
+// accepted under capture, and the apply that must then rebuild is refused there, as any build is.  Reset keeps the value.
+int PostProcessor::SetHdrDomain(int domain)
+{
+    hdrDomain_ = domain;
+    sequence_.Reset(true);
+    enabled_ = true;
+    replan_ = true;
+    return OVRFSR_OK;
+}
+
 int PostProcessor::HiddenAreaStats(int eye, uint32_t *tilesTotal, uint32_t *tilesSkipped)
 {
-    if (!initialized_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "no plan yet: hidden-area statistics follow a successful apply");
+    if (!initialized_ || replan_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "no plan yet: hidden-area statistics follow a successful apply");
     *tilesTotal = plan_.grid.tiles(); // tiles per image as the plan's lists count them
     *tilesSkipped = plan_.hiddenArea ? plan_.nSkipped[eye & 1] : 0u;
     return OVRFSR_OK;
@@ -251,9 +265,10 @@ int PostProcessor::IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midS
 // configuration allocates nothing.  What the plan holds is then created on the device, in a fixed order (fault injection counts creations).
 int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneEye)
 {
+    replan_ = false; // (asked for before anything was built: this is that plan)
     HiddenArea hidden;
     for (int eye = 0; eye < 2; ++eye) { hidden.uv[eye] = hiddenUv_[eye].data(); hidden.triangles[eye] = (uint32_t)(hiddenUv_[eye].size() / 6); }
-    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden);
+    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden, hdrDomain_);
     if (refused) return Fail(refused.status, refused.text);
     if (plan_.useNis) { // coef_scale[512] | coef_usm[512], PostProcessor.cpp:366-382
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
@@ -625,14 +640,38 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
         if (timing) (void)hipEventRecord(queries_[currentQuery_].start, stream); // (behind the re-order, which the timer has never covered)
     }
 
+    // OVRFSR_HDR_DOMAIN_SRTM (header, "HDR domain"): the pipeline reads a ctx-owned RGBA32F copy of its input holding the mapped values and
+    // writes a second ctx-owned RGBA32F image, which the back pass behind the switch un-maps into `out`.  Both tight, image after image; the
+    // plan is the RGBA32F submission's (plan_pipeline), and the timer, started above, brackets both passes.
+    ovrfsr_image pipeOut = out;
+    size_t pipeOutStride = outStride;
+    const bool hdr = plan_.hdrDomain && plan_.form != Form::None;
+    if (hdr) {
+        const size_t mappedStride = (size_t)in.width * in.height * 16u;
+        pipeOut.format = OVRFSR_FORMAT_RGBA32F;
+        pipeOut.pitch_bytes = out.width * 16u;
+        pipeOutStride = (size_t)pipeOut.pitch_bytes * out.height;
+        int rc = EnsureBuffer(hdrIn_, mappedStride * n);
+        if (rc == OVRFSR_OK) rc = EnsureBuffer(hdrOut_, pipeOutStride * n);
+        if (rc != OVRFSR_OK) return rc;
+        rc = Launched(launch_hdr_forward((int)in.format, static_cast<const uint8_t *>(in.data), in.pitch_bytes, inStride, static_cast<uint8_t *>(hdrIn_.p),
+                                         in.width, in.height, n, stream), "HDR forward map");
+        if (rc != OVRFSR_OK) return rc;
+        in.format = OVRFSR_FORMAT_RGBA32F;
+        in.pitch_bytes = in.width * 16u;
+        inStride = mappedStride;
+        in.data = hdrIn_.p;
+        pipeOut.data = hdrOut_.p;
+    }
+
     int rc = OVRFSR_OK;
     switch (plan_.form) {
     case Form::MaskSorted:
-        rc = ApplySorted(n, firstEye, alternate, in, inStride, out, outStride, stream);
+        rc = ApplySorted(n, firstEye, alternate, in, inStride, pipeOut, pipeOutStride, stream);
         break;
     case Form::Fused:
     case Form::FusedMaskedOutside:
-        rc = ApplyFused(n, firstEye, alternate, in, inStride, out, outStride, stream);
+        rc = ApplyFused(n, firstEye, alternate, in, inStride, pipeOut, pipeOutStride, stream);
         break;
     case Form::TwoPass: {
         ovrfsr_image mid;
@@ -640,18 +679,21 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
         rc = IntermediateImage(n, &mid, &midStride);
         if (rc != OVRFSR_OK) return rc;
         rc = ApplyUpscaling(n, firstEye, alternate, in, inStride, mid, midStride, stream);
-        if (rc == OVRFSR_OK) rc = ApplySharpening(n, firstEye, alternate, mid, midStride, out, outStride, stream);
+        if (rc == OVRFSR_OK) rc = ApplySharpening(n, firstEye, alternate, mid, midStride, pipeOut, pipeOutStride, stream);
         break;
     }
     case Form::UpscaleOnly:
-        rc = ApplyUpscaling(n, firstEye, alternate, in, inStride, out, outStride, stream);
+        rc = ApplyUpscaling(n, firstEye, alternate, in, inStride, pipeOut, pipeOutStride, stream);
         break;
     case Form::SharpenOnly:
-        rc = ApplySharpening(n, firstEye, alternate, in, inStride, out, outStride, stream);
+        rc = ApplySharpening(n, firstEye, alternate, in, inStride, pipeOut, pipeOutStride, stream);
         break;
     case Form::None:
         break;
     }
+    if (hdr && rc == OVRFSR_OK)
+        rc = Launched(launch_hdr_back((int)out.format, static_cast<const uint8_t *>(hdrOut_.p), static_cast<uint8_t *>(out.data), out.pitch_bytes, outStride,
+                                      out.width, out.height, n, stream), "HDR back map");
     if (timing) {
         (void)hipEventRecord(queries_[currentQuery_].end, stream);
         queries_[currentQuery_].pending = true;
@@ -677,7 +719,7 @@ int PostProcessor::FlushPending(hipStream_t stream, bool *ownedOutput)
 // is the plan still for this input?  (a batch call also asks whether its images hold one eye or both, as the plan assumes)
 bool PostProcessor::PlannedFor(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const
 {
-    return initialized_ && in.width == plan_.inputWidth && in.height == plan_.inputHeight && in.format == plan_.inputFormat &&
+    return initialized_ && !replan_ && in.width == plan_.inputWidth && in.height == plan_.inputHeight && in.format == plan_.inputFormat &&
            (!compareEyeLayout || plan_.onlyOneEye == onlyOneEye);
 }
 

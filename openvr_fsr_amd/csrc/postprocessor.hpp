@@ -44,6 +44,9 @@ public:
     // ovrfsr_set_hidden_area / ovrfsr_hidden_area_stats behind their argument checks
     int SetHiddenArea(int eye, const float *uv, uint32_t triangles);
     int HiddenAreaStats(int eye, uint32_t *tilesTotal, uint32_t *tilesSkipped);
+    // ovrfsr_set_hdr_domain / ovrfsr_get_hdr_domain behind their argument checks
+    int SetHdrDomain(int domain);
+    int HdrDomain() const { return hdrDomain_; }
     int LastGpuTimeMs(float *ms);
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
@@ -52,6 +55,7 @@ private:
     ovrfsr_config cfg_;
     std::string lastError_;
     std::vector<float> hiddenUv_[2]; // the hidden-area mesh of each eye, 6 floats per triangle: outlives Reset and SetConfig (header)
+    int hdrDomain_ = OVRFSR_HDR_DOMAIN_LINEAR; // ovrfsr_set_hdr_domain's value: outlives Reset and SetConfig too
 
     // PostProcessor.h:16-24
     bool enabled_ = true;
@@ -73,6 +77,7 @@ private:
     // a ctx-owned auxiliary stream, forked from and joined back into the caller's stream with events
     hipStream_t auxStream_ = nullptr;
     hipEvent_t evFork_ = nullptr, evJoin_ = nullptr;
+    bool replan_ = false;     // ovrfsr_set_hdr_domain asked for a fresh plan: no plan is "for" any input until the next apply has reset and rebuilt
     bool capturing_ = false;  // the stream of the call in progress is being captured into a HIP graph: launches only, no (re)build
     DeviceBuffer retired_;    // a ctx-owned output image a flushed pair_submit eye was handed in, kept across the rebuild of a size change
     void ResetKeeping(bool keepRetired);
@@ -93,6 +98,7 @@ private:
     DeviceBuffer resolved_;  // single-sample copy of a multisampled submission, RGBA16F copy of an R11G11B10F one that is not decoded in staging (rows padded to 16 B), see ApplyPostProcess
     DeviceBuffer upscaled_;
     DeviceBuffer sharpened_;
+    DeviceBuffer hdrIn_, hdrOut_; // Plan::hdrDomain: the mapped RGBA32F copy the pipeline reads and the RGBA32F image it writes (tight rows, image after image), see ApplyPostProcess
 
     // debug-mode GPU timing, PostProcessor.h:72-82: a ring of kQueryCount timestamp pairs; after every apply the OLDEST
     // slot is read back (so the wait is normally over already), durations are summed and every 500 readings the mean

@@ -132,6 +132,17 @@ class PostProcessor:
         self._check(self._lib.ovrfsr_hidden_area_stats(self._ctx, int(eye), C.byref(total), C.byref(skipped)))
         return total.value, skipped.value
 
+    def set_hdr_domain(self, domain):
+        """ovrfsr_set_hdr_domain: K.HDR_DOMAIN_LINEAR (default) or K.HDR_DOMAIN_SRTM -- float submissions are tone-mapped in front of the
+        filters and un-mapped behind them.  The next apply rebuilds."""
+        self._check(self._lib.ovrfsr_set_hdr_domain(self._ctx, int(domain)))
+
+    def hdr_domain(self):
+        """ovrfsr_get_hdr_domain"""
+        d = C.c_int()
+        self._check(self._lib.ovrfsr_get_hdr_domain(self._ctx, C.byref(d)))
+        return d.value
+
     def last_gpu_time_ms(self):
         ms = C.c_float()
         self._check(self._lib.ovrfsr_last_gpu_time_ms(self._ctx, C.byref(ms)))
