@@ -462,6 +462,45 @@ OVRFSR_API int ovrfsr_get_hdr_domain(const ovrfsr_ctx *ctx, int *domain);
  * (inverse = 0) or back (inverse = 1).  OVRFSR_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer with n > 0 or any other `inverse`. */
 OVRFSR_API int ovrfsr_hdr_map(const float *rgb_in, float *rgb_out, size_t n, int inverse);
 
+/* ---- eye-tracked foveation: the radius mask follows the gaze, per frame ----------------------------------
+ * cfg.proj_centre fixes the centre of the sharp disc per eye, as the reference does.  A headset with eye tracking wants the disc where the
+ * eye looks, every frame; ovrfsr_set_config moves it too, but it is a reset: everything freed, re-planned and uploaded again.  A gaze moves
+ * the centre and nothing else.  No ABI version and no config field changes with these: a host probes for the symbols.
+ *
+ * x, y: proj_centre's convention and range -- [0, 1] of ONE eye's image, y = 0 at the first stored row, accepted in [-1, 2].
+ *
+ * THE RULE.  With a gaze set for eye e, every call behaves as the same call on a fresh ctx whose cfg.proj_centre holds the gaze in eye e's
+ * two slots (the two centres of a shared side-by-side texture go through ovrfsr_mask_constants as they do today): status, error text,
+ * the image handed back, every byte written, ovrfsr_hidden_area_stats -- in every form, format, build and precision, for batches (eye e's
+ * gaze applies to every image of that eye), pair_submit, hidden-area meshes and OVRFSR_HDR_DOMAIN_SRTM.  ovrfsr_clear_gaze returns the eye
+ * to cfg.proj_centre.  ovrfsr_reset and ovrfsr_set_config keep the gaze.
+ *
+ * LATCHING.  The gaze is read by the apply that launches the eye.  Unlike the other setters, ovrfsr_set_gaze drops no recorded pair_submit
+ * eye, re-enables no disabled ctx and forces no rebuild by itself; a recorded pair launches with the gazes in effect at its SECOND call.
+ * Set both eyes' gazes before the frame's first apply.
+ *
+ * WHAT AN APPLY AFTER A GAZE CHANGE DOES, one of three (ovrfsr_gaze_stats counts the second and the third):
+ *   - nothing: the mask centres, integers in output pixels, are the current ones (0.5 -> 0.5001 at width 160);
+ *   - a RE-AIM in place: only the centres, the per-eye mask modes and the tile lists move.  No allocation, no blocking copy, no host wait
+ *     (the new lists go through a small ring of pinned staging slots on the call's stream; the host waits only where the host is more
+ *     than the ring's four uploads ahead of the device), the ctx-owned output and intermediate images stay where they are;
+ *   - a REBUILD of the ctx's tables: the mask moved between "mixed" and "no tile inside / every tile inside" (both gazes at (2, 2)), or the
+ *     gaze was set on a ctx planned without one.  Sizes and formats do not move with a gaze, so the images the ctx owns and a recorded
+ *     pair_submit eye keep their place; a rebuild that fails disables the ctx until reset, like any failed build, and one that runs out of
+ *     memory answers OVRFSR_ERR_OUT_OF_MEMORY.
+ * Under stream capture the setter is accepted; an apply that would re-aim or rebuild is refused like any build (OVRFSR_ERR_INVALID_ARGUMENT,
+ * nothing touched, the capture stays valid, the gaze stays pending): make the call once outside the capture.  A captured graph replays the
+ * gaze it was captured with.  A ctx on which no gaze was ever set allocates, uploads and launches exactly what it always has.
+ *
+ * OVRFSR_ERR_INVALID_ARGUMENT -- the stored value left as it was -- for a NULL ctx, an eye other than OVRFSR_EYE_LEFT / OVRFSR_EYE_RIGHT, or
+ * a coordinate that is NaN, infinite or outside [-1, 2]. */
+OVRFSR_API int ovrfsr_set_gaze(ovrfsr_ctx *ctx, int eye, float x, float y);
+OVRFSR_API int ovrfsr_clear_gaze(ovrfsr_ctx *ctx, int eye);
+/* xy: the gaze, or the eye's cfg.proj_centre where none is set (*is_set = 0).  OVRFSR_ERR_INVALID_ARGUMENT for a NULL argument or a bad eye. */
+OVRFSR_API int ovrfsr_get_gaze(const ovrfsr_ctx *ctx, int eye, float xy[2], int *is_set);
+/* re-aims in place and rebuilds that applies performed because of a gaze, since the ctx was created */
+OVRFSR_API int ovrfsr_gaze_stats(const ovrfsr_ctx *ctx, uint32_t *reaims, uint32_t *rebuilds);
+
 /* ---- constants-only entry points (known-answer tests; no GPU needed) ------------------------- */
 
 /* FsrEasuCon (src/fsr/ffx_fsr1.h:156-202); con = con0|con1|con2|con3 */

@@ -125,6 +125,11 @@ def library():
         L.ovrfsr_set_hdr_domain.argtypes = [C.c_void_p, C.c_int]
         L.ovrfsr_get_hdr_domain.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.ovrfsr_hdr_map.argtypes = [f32p, f32p, C.c_size_t, C.c_int]
+    if hasattr(L, "ovrfsr_set_gaze"):  # (probed the same way)
+        L.ovrfsr_set_gaze.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        L.ovrfsr_clear_gaze.argtypes = [C.c_void_p, C.c_int]
+        L.ovrfsr_get_gaze.argtypes = [C.c_void_p, C.c_int, f32p, C.POINTER(C.c_int)]
+        L.ovrfsr_gaze_stats.argtypes = [C.c_void_p, u32p, u32p]
     if L.ovrfsr_abi_version() != 5:
         raise OvrFsrError(1, "ABI version mismatch")
     _LIB = L

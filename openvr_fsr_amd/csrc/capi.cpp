@@ -145,6 +145,40 @@ OVRFSR_API int ovrfsr_get_hdr_domain(const ovrfsr_ctx *ctx, int *domain)
     return OVRFSR_OK;
 }
 
+// ---- eye-tracked foveation (header).  The argument checks live here; the setters store, the next apply acts (PostProcessor::AimGaze).
+namespace {
+bool eye_ok(int eye) { return eye == OVRFSR_EYE_LEFT || eye == OVRFSR_EYE_RIGHT; }
+bool centre_ok(float c) { return c >= -1.0f && c <= 2.0f; } // proj_centre's range (floats_valid); NaN and the infinities fail the comparison
+} // namespace
+
+OVRFSR_API int ovrfsr_set_gaze(ovrfsr_ctx *ctx, int eye, float x, float y)
+{
+    if (!ctx || !eye_ok(eye) || !centre_ok(x) || !centre_ok(y)) return OVRFSR_ERR_INVALID_ARGUMENT; // the stored value stays
+    ctx->pp->SetGaze(eye, x, y);
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_clear_gaze(ovrfsr_ctx *ctx, int eye)
+{
+    if (!ctx || !eye_ok(eye)) return OVRFSR_ERR_INVALID_ARGUMENT;
+    ctx->pp->ClearGaze(eye);
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_get_gaze(const ovrfsr_ctx *ctx, int eye, float xy[2], int *is_set)
+{
+    if (!ctx || !eye_ok(eye) || !xy || !is_set) return OVRFSR_ERR_INVALID_ARGUMENT;
+    ctx->pp->GetGaze(eye, xy, is_set);
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_gaze_stats(const ovrfsr_ctx *ctx, uint32_t *reaims, uint32_t *rebuilds)
+{
+    if (!ctx || !reaims || !rebuilds) return OVRFSR_ERR_INVALID_ARGUMENT;
+    ctx->pp->GazeStats(reaims, rebuilds);
+    return OVRFSR_OK;
+}
+
 OVRFSR_API int ovrfsr_hdr_map(const float *rgb_in, float *rgb_out, size_t n, int inverse)
 {
     if ((n && (!rgb_in || !rgb_out)) || (inverse != 0 && inverse != 1)) return OVRFSR_ERR_INVALID_ARGUMENT; // (nothing written)

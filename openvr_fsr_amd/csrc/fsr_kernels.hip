@@ -517,6 +517,8 @@ hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t src
 // The forward and back passes of OVRFSR_HDR_DOMAIN_SRTM with their launchers: a file of their own inside this unit (it opens its own
 // namespaces).  Here, in front of launch_rcas, so that the kernels launch_rcas instantiates stay the last ones of the code object.
 #include "fsr_hdr_domain.inc"
+// ... and the tile records of a gaze-capable ctx, built on the device (tile_records_kernel), likewise
+#include "fsr_tile_records.inc"
 namespace ovrfsr {
 
 #ifdef OVRFSR_BOUNDS

@@ -39,6 +39,8 @@ hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t src
 // OVRFSR_HDR_DOMAIN_SRTM (fsr_hdr_domain.inc): fmt RGBA16F / RGBA32F pipeline input -> tight RGBA32F copy, mapped; and that layout back into an RGBA8 / RGBA16F / RGBA32F destination, un-mapped
 hipError_t launch_hdr_forward(int fmt, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h, uint32_t batch, hipStream_t s);
 hipError_t launch_hdr_back(int fmt, const uint8_t *src, uint8_t *dst, uint32_t dstPitch, uint64_t dstStride, uint32_t w, uint32_t h, uint32_t batch, hipStream_t s);
+// the 16-byte records of the first a.n[eye] entries of both list regions (fsr_tile_records.inc); no launch where both are empty
+hipError_t launch_tile_records(const TileRecordsArgs &a, hipStream_t s);
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a, uint32_t nGroups, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s);

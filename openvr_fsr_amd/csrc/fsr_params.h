@@ -4,6 +4,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "tile_records.h"
 
 namespace ovrfsr {
 
@@ -106,6 +107,18 @@ struct OutsideArgs {
                                  // colsN | rowsN << 8, 0 -- tile origin, footprint origin and extent (see outside_staged_kernel)
     uint32_t nTiles;             // list length; the kernel is persistent: block b walks entries b, b + gridDim.x, ...
     OVRFSR_ARGS_LDS_BYTES
+};
+
+// tile_records_kernel (fsr_tile_records.inc): the records of a gaze-capable ctx's list entries, built where the lists were uploaded to.
+// lists: two per-eye regions of regionEntries tile indices each, of which the first n[eye] are in use; recs: 4 dwords per entry, parallel.
+struct TileRecordsArgs {
+    const uint32_t *lists;
+    uint32_t *recs;
+    const BilinTap *bilX;     // [g.outW], [g.outH]
+    const BilinTap *bilY;
+    TileRecordGrid g;
+    uint32_t regionEntries;
+    uint32_t n[2];
 };
 
 struct RcasArgs {

@@ -2,7 +2,9 @@
 // nis_config.cpp alone.  Reference: src/postprocess/PostProcessor.cpp (PrepareResources and what it calls).
 #include "pipeline_plan.h"
 #include <algorithm>
+#include <cassert>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <utility>
 #include "fsr_formats.h"
@@ -273,17 +275,15 @@ void hidden_tiles(const float *left, uint32_t leftTriangles, const float *right,
 namespace {
 
 // ---- the tile lists ----------------------------------------------------------------------------------------------------------------------
-// The radius mask is static per eye, so the tiles are sorted once on the host: tiles with at least one mask group inside the radius (EASU
-// kernel, LDS-staged) and tiles entirely outside (bilinear only, LDS-free kernel); under a hidden-area mesh, the tiles no lens shows are in
-// neither list.  tile_lists() builds them in the steps below, each with one job; all of them run at plan time only.
+// The radius mask moves only where the host moves it -- never on a ctx without a gaze, per frame at most on one with eye tracking
+// (ovrfsr_set_gaze) --, so the tiles are sorted on the host: tiles with at least one mask group inside the radius (EASU kernel, LDS-staged)
+// and tiles entirely outside (bilinear only, LDS-free kernel); under a hidden-area mesh, the tiles no lens shows are in neither list.
+// tile_lists() builds them in the steps below, each with one job; they run at plan time, and steps 1-5 again when a gaze re-aims the
+// mask (reaim_pipeline).
 
 // one eye's tiles by class, each in raster order
 struct TileClasses {
     std::vector<uint32_t> inside, outside, hidden;
-};
-// per eye, a byte per tile of the grid (hidden_tiles); empty: no mesh in effect
-struct HiddenMaps {
-    std::vector<uint8_t> eye[2];
 };
 
 // one eye per texture: each eye's own mesh; a shared side-by-side texture: one map of both halves, the same for both "eyes"
@@ -410,46 +410,68 @@ void pack_lists(Plan &p, int eye, const TileClasses &c, const std::vector<uint32
 
 // Step 6.  One record per list entry for the persistent outside-tile kernel (outside_staged_kernel): tile origin, footprint origin (first
 // column / row tap) and extent ([first tap, last tap + 1], what the kernel used to fetch through a chain of dependent scalar loads: tile
-// index -> tap tables).  Reads the plan's grid, tap tables and lists; writes nothing of it.
-std::vector<uint32_t> outside_records(const Plan &p)
+// index -> tap tables): tile_record (tile_records.h), which tile_records_kernel evaluates too.  Reads the plan's grid and lists and the
+// tap tables of `tables` (the plan itself, or the one a re-aimed plan left them with); writes nothing.
+std::vector<uint32_t> outside_records(const Plan &p, const Plan &tables)
 {
-    const TileGrid &g = p.grid;
-    const uint32_t outW = p.outputWidth, outH = p.outputHeight;
+    const TileRecordGrid g = record_grid(p);
     std::vector<uint32_t> recs(p.lists.size() * 4, 0u);
-    const BilinTap *bx = p.taps.data(), *by = p.taps.data() + p.tapYOff;
-    const uint32_t rowsCap = p.outsideRows[g.tileH == (uint32_t)kTileH ? 0 : 1];
+    const BilinTap *bx = tables.taps.data(), *by = tables.taps.data() + p.tapYOff;
     for (size_t i = 0; i < p.lists.size(); ++i) {
-        const uint32_t t = p.lists[i], tyi = t / g.tx, txi = t - tyi * g.tx;
-        const uint32_t ox0 = txi * g.tileW, oy0 = tyi * g.tileH;
-        const int X0 = bx[ox0].i0, Y0 = by[oy0].i0;
-        const int colsN = std::min<int>((int)p.outsideCols, bx[std::min(ox0 + g.tileW - 1, outW - 1)].i0 + 2 - X0);
-        const int rowsN = std::min<int>((int)rowsCap, by[std::min(oy0 + g.tileH - 1, outH - 1)].i0 + 2 - Y0);
-        recs[4 * i + 0] = ox0 | (oy0 << 16);
-        recs[4 * i + 1] = (uint32_t)(X0 + 1) | ((uint32_t)(Y0 + 1) << 16);
-        recs[4 * i + 2] = (uint32_t)colsN | ((uint32_t)rowsN << 8);
+        const TileRecord r = tile_record(p.lists[i], g, bx, by);
+        std::copy(r.w, r.w + 4, recs.begin() + 4 * i);
     }
     return recs;
 }
 
-// The six steps, per eye, over p.grid; what steers them is the plan's own: maskLists, hiddenArea (with `hidden`, its per-eye maps) and form.
-void tile_lists(Plan &p, const HiddenMaps &hidden)
+// Is RCAS handed a list of its own (two-pass under a mesh), and are span records cut -- wherever the tiles are the span kernel's and its
+// packing holds them?  Both follow from fields no gaze moves.
+bool rcas_own_list(const PlanFields &p) { return p.hiddenArea && p.form == Form::TwoPass; }
+bool cut_spans(const PlanFields &p)
 {
     const TileGrid &g = p.grid;
-    // two-pass under a mesh: RCAS gets a list of its own.  Spans: wherever the tiles are the span kernel's and its packing holds them
-    const bool rcasOwnList = p.hiddenArea && p.form == Form::TwoPass;
-    const bool cutSpans = g.tileW == (uint32_t)kTileW && g.tileH == (uint32_t)kRcasDppTileH && p.outputWidth < 65536u && g.ty < 65536u;
+    return g.tileW == (uint32_t)kTileW && g.tileH == (uint32_t)kRcasDppTileH && p.outputWidth < 65536u && g.ty < 65536u;
+}
+
+// The regions of a gaze-capable plan, from grid.tiles() and outW, for ANY mask centre.  Lists: inside, outside and hidden tiles are disjoint
+// and the ring is a subset of outside + hidden, so inside | ring | outside hold at most 2 * tiles entries, RCAS's own list (every visible
+// tile) at most tiles more; rounded up to 4 entries, so that every region's records start 16-byte aligned.  Spans: a run of k adjacent
+// 32-wide tiles is cut into ceil(32 k / 62) <= k segments (cut_spans: outW < 65536, so the packing holds), the runs of an eye are disjoint:
+// at most tiles segments.
+void gaze_regions(PlanFields &p)
+{
+    const size_t tiles = p.grid.tiles();
+    static_assert(kRcasDppTileW >= kTileW, "a run of k tiles is cut into at most k segments");
+    p.listRegion = ((rcas_own_list(p) ? 3 : 2) * tiles + 3) & ~(size_t)3;
+    p.spanRegion = cut_spans(p) ? tiles : 0;
+}
+
+// The steps, per eye, over p.grid; what steers them is the plan's own: maskLists, hiddenArea (with `hidden`, its per-eye maps) and form.
+// Step 6 on the host only where `tables` (the plan holding the tap tables) is given.  A gaze-capable plan: every eye's lists and segments
+// start at its region, the bound asserted.
+void tile_lists(Plan &p, const HiddenMaps &hidden, const Plan *tables)
+{
+    const TileGrid &g = p.grid;
+    const bool rcasOwnList = rcas_own_list(p), cutSpans = cut_spans(p);
     TileClasses c[2];
     std::vector<uint32_t> ring[2];
     for (int eye = 0; eye < 2; ++eye) {
+        if (p.gazeCapable) { p.lists.resize((size_t)eye * p.listRegion, 0u); p.spans.resize(2 * (size_t)eye * p.spanRegion, 0u); }
         c[eye] = classify_tiles(g, p.centre[eye], p.radius[1], p.maskLists, hidden.eye[eye]);
         const std::vector<uint32_t> rcas = rcas_tiles(c[eye], rcasOwnList);
         ring[eye] = ring_tiles(g, rcas, ring_candidates(c[eye], rcasOwnList, p.hiddenArea && p.form == Form::MaskSorted));
         if (cutSpans) rcas_spans(g, p.outputWidth, rcas, p.spans, &p.spanOff[eye], &p.nSpans[eye]);
         pack_lists(p, eye, c[eye], ring[eye], rcasOwnList ? &rcas : nullptr);
+        if (p.gazeCapable) {
+            const bool fits = p.lists.size() <= (size_t)(eye + 1) * p.listRegion && p.spans.size() <= 2 * (size_t)(eye + 1) * p.spanRegion;
+            assert(fits && "a gaze-capable plan's lists left their region");
+            if (!fits) std::abort(); // (also where assert is compiled out: the device allocation is sized by the regions)
+        }
     }
+    if (p.gazeCapable) { p.lists.resize(2 * p.listRegion, 0u); p.spans.resize(4 * p.spanRegion, 0u); }
     // (the final lists: without a mesh outside and ring follow from inside)
     p.listsShared = c[0].inside == c[1].inside && c[0].outside == c[1].outside && ring[0] == ring[1];
-    p.recs = outside_records(p);
+    if (tables) p.recs = outside_records(p, *tables);
 }
 
 // Near-tie guard of a half-float intermediate: the smallest value whose flipped half rounding could exceed the 1e-3 tolerance
@@ -466,6 +488,12 @@ float tie_half_min(const ovrfsr_config &cfg, const Plan &p)
 }
 
 } // namespace
+
+TileRecordGrid record_grid(const PlanFields &p)
+{
+    const TileGrid &g = p.grid;
+    return TileRecordGrid{g.tx, g.tileW, g.tileH, p.outputWidth, p.outputHeight, p.outsideCols, p.outsideRows[g.tileH == (uint32_t)kTileH ? 0 : 1]};
+}
 
 const Refusal *plan_refusals(size_t *count)
 {
@@ -524,7 +552,7 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
 
 // the plan of one submission as it is filtered: what plan_pipeline has always been
 static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                             const HiddenArea *hidden)
+                             const HiddenArea *hidden, HiddenMaps *gaze)
 {
     Plan p;
     p.inputWidth = width; p.inputHeight = height; p.inputFormat = format;
@@ -567,7 +595,7 @@ static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t
 
     for (int eye = 0; eye < 2; ++eye) {
         mask_constants(p.centre[eye], p.radius, ow, oh, cfg.proj_centre, cfg.radius, onlyOneEye ? 1 : 0, eye);
-        const uint32_t gw = cfg.use_nis ? 32u : 16u, gh = cfg.use_nis ? (scaleNotOne ? 24u : 32u) : 16u;
+        const uint32_t gw = p.maskGroupW = cfg.use_nis ? 32u : 16u, gh = p.maskGroupH = cfg.use_nis ? (scaleNotOne ? 24u : 32u) : 16u;
         p.maskMode[eye] = classify_mask(p.centre[eye], p.radius[1], ow, oh, gw, gh);
     }
     if (cfg.use_nis) {
@@ -640,20 +668,27 @@ static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t
     v.inW = (int32_t)width; v.inH = (int32_t)height; v.outW = (int32_t)ow; v.outH = (int32_t)oh;
     p.overlapOutside = p.maskLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
 
-    if (p.tileLists) tile_lists(p, p.hiddenArea ? hidden_maps(p, *hidden) : HiddenMaps{});
+    HiddenMaps maps;
+    if (p.hiddenArea) maps = hidden_maps(p, *hidden);
+    if (gaze) {
+        p.gazeCapable = true;
+        gaze_regions(p);
+    }
+    if (p.tileLists) tile_lists(p, maps, &p);
+    if (gaze) *gaze = std::move(maps);
     *plan = std::move(p);
     return Refusal{};
 }
 
 Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden, int hdrDomain)
+                      const HiddenArea *hidden, int hdrDomain, HiddenMaps *gaze)
 {
     const uint32_t pf = pipeline_format(format);
     if (hdrDomain == OVRFSR_HDR_DOMAIN_SRTM && (pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F)) {
         // FSR 1's reversible tone-mapped domain (header, "HDR domain"): the pipeline is the RGBA32F submission's, between a forward pass that
         // writes its input and a back pass that reads its result, both ctx-owned RGBA32F images.  No mesh: the back pass walks whole images.
         Plan p;
-        if (!plan_filtered(cfg, OVRFSR_FORMAT_RGBA32F, width, height, onlyOneEye, &p, nullptr)) {
+        if (!plan_filtered(cfg, OVRFSR_FORMAT_RGBA32F, width, height, onlyOneEye, &p, nullptr, gaze)) {
             p.hdrDomain = true;
             p.inputFormat = format;                                                    // what the plan is FOR (PostProcessor::PlannedFor)
             p.ownedFormat = cfg.reference_formats ? reference_output_format(pf) : pf;  // the submission's own rule
@@ -663,7 +698,31 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
         }
         // (refused as RGBA32F: whatever the submission itself gets -- the same refusal, or its own plan with the setting not applied)
     }
-    return plan_filtered(cfg, format, width, height, onlyOneEye, plan, hidden);
+    return plan_filtered(cfg, format, width, height, onlyOneEye, plan, hidden, gaze);
+}
+
+Reaim reaim_pipeline(const Plan &current, const ovrfsr_config &effective, const HiddenMaps &hidden, Plan *reaimed, bool hostRecords)
+{
+    const PlanFields &c = current;
+    uint32_t centre[2][4], radius[4], mode[2];
+    for (int eye = 0; eye < 2; ++eye) {
+        mask_constants(centre[eye], radius, c.outputWidth, c.outputHeight, effective.proj_centre, effective.radius, c.onlyOneEye ? 1 : 0, eye);
+        mode[eye] = classify_mask(centre[eye], radius[1], c.outputWidth, c.outputHeight, c.maskGroupW, c.maskGroupH);
+    }
+    if (!std::memcmp(centre, c.centre, sizeof centre)) return Reaim::Nothing; // (the same centres: the same modes and lists)
+    // what plan_pipeline derives from the modes: maskLists -- and from it tileLists, the form and overlapOutside --, and resolve_in_staging's
+    // "every group of both eyes is inside the radius"
+    const bool maskLists = c.doUpscale && c.launchPrec == PREC_FP32 && (mode[0] == MASK_MIXED || mode[1] == MASK_MIXED);
+    const bool allInside = mode[0] == MASK_ALL_INSIDE && mode[1] == MASK_ALL_INSIDE;
+    const bool wasAllInside = c.maskMode[0] == MASK_ALL_INSIDE && c.maskMode[1] == MASK_ALL_INSIDE;
+    if (!c.gazeCapable || maskLists != c.maskLists || allInside != wasAllInside) return Reaim::Rebuild;
+    Plan p;
+    static_cast<PlanFields &>(p) = c;
+    std::memcpy(p.centre, centre, sizeof centre);
+    p.maskMode[0] = mode[0]; p.maskMode[1] = mode[1];
+    if (p.tileLists) tile_lists(p, hidden, hostRecords ? &current : nullptr);
+    *reaimed = std::move(p);
+    return Reaim::InPlace;
 }
 
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat)

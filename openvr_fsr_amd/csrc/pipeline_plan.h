@@ -53,7 +53,8 @@ struct TileGrid {
 };
 TileGrid tile_grid(bool useNis, bool doUpscale, uint32_t outW, uint32_t outH);
 
-struct Plan {
+// Everything of a Plan but its tables: plain values, copied freely (the re-aim step hands back a Plan without the tap tables)
+struct PlanFields {
     // what was planned for: the canonical submitted format (a multisampled encoding included), its size, one eye per texture or both
     uint32_t inputWidth = 0, inputHeight = 0, inputFormat = 0;
     bool onlyOneEye = true;
@@ -89,9 +90,8 @@ struct Plan {
     int nisCellsW = 0, nisCellsH = 0;     // ... of one 32x24 NVScaler group
     float rcpOut[2] = {0, 0};    // RN(1/outW), RN(1/outH) and whether mul+2fma reproduces o/out for every o (div_exact)
     bool rcpExact = false;
-    // bilinear fallback / DirectCopy taps: [outW column taps, padded to a multiple of the tile width with copies of the last | outH row taps
-    // at tapYOff | 64 spare entries]
-    std::vector<BilinTap> taps;
+    // bilinear fallback / DirectCopy taps (Plan::taps): [outW column taps, padded to a multiple of the tile width with copies of the last |
+    // outH row taps at tapYOff | 64 spare entries]
     uint32_t tapYOff = 0;
     uint32_t outsideCols = 0, outsideRows[2] = {0, 0}; // bilinear footprint bound of a 32-wide tile; rows for 32- and 24-row tiles
     // the tile grid of the output: what the launches' tilesX / tilesY are, what the lists below index
@@ -99,8 +99,7 @@ struct Plan {
     // the tile lists, per eye: Plan::lists holds inside | ring | outside (| rcas) -- the ring tiles follow the inside tiles so that ONE EASU
     // launch over nInside + nRing entries also writes the intermediate of the ring, while RCAS walks the inside tiles only (ring: tiles
     // 4-adjacent to a tile RCAS processes whose intermediate no other launch writes); one 4-dword record per list entry
-    // (OutsideArgs::tileRec); RCAS segments of the runs RCAS walks, 2 dwords each (RcasArgs::spanRec)
-    std::vector<uint32_t> lists, recs, spans; // (PostProcessor frees these three once they are uploaded; the counts and offsets stay)
+    // (OutsideArgs::tileRec); RCAS segments of the runs RCAS walks, 2 dwords each (RcasArgs::spanRec): Plan::lists, recs, spans
     uint32_t nInside[2] = {0, 0}, nOutside[2] = {0, 0}, nRing[2] = {0, 0}, nSpans[2] = {0, 0};
     size_t listOffInside[2] = {0, 0}, listOffOutside[2] = {0, 0}, listOffRing[2] = {0, 0}, spanOff[2] = {0, 0}; // spanOff in segments
     // what RCAS walks: the inside segment itself, or (two-pass under a hidden-area mesh) a fourth segment of its own -- every tile that is
@@ -109,6 +108,17 @@ struct Plan {
     size_t listOffRcas[2] = {0, 0};
     uint32_t nSkipped[2] = {0, 0}; // hiddenArea: tiles no launch writes the destination of (a hidden ring tile is still a skipped one)
     bool listsShared = false;    // both eyes have identical lists
+    // A gaze-capable plan (plan_pipeline, `gaze`): the lists and the spans live in fixed per-eye regions sized for the worst case of any gaze, so
+    // that reaim_pipeline's result fits where the current lists are -- eye e's lists start at e * listRegion (entries), its segments at
+    // e * spanRegion (segments); what a region does not use is zero.  maskGroupW / H: the groups classify_mask tests the radius on.
+    bool gazeCapable = false;
+    size_t listRegion = 0, spanRegion = 0;
+    uint32_t maskGroupW = 0, maskGroupH = 0;
+};
+
+struct Plan : PlanFields {
+    std::vector<BilinTap> taps;
+    std::vector<uint32_t> lists, recs, spans; // (PostProcessor frees these three once they are uploaded; the counts and offsets stay)
 };
 
 // ovrfsr_set_hidden_area's meshes as the planner takes them: per eye, `triangles` triangles of 3 x (u, v) floats (header: the rule)
@@ -122,6 +132,14 @@ struct HiddenArea {
 void hidden_tiles(const float *left, uint32_t leftTriangles, const float *right, uint32_t rightTriangles, bool shared, uint32_t outW, uint32_t outH,
                   uint32_t tileW, uint32_t tileH, uint8_t *hidden);
 
+// per eye, a byte per tile of the grid (hidden_tiles); empty: no mesh in effect
+struct HiddenMaps {
+    std::vector<uint8_t> eye[2];
+};
+
+// what tile_record (tile_records.h) computes a plan's records from, on the host (outside_records) and on the device (tile_records_kernel)
+TileRecordGrid record_grid(const PlanFields &p);
+
 // ovrfsr_output_size behind its argument checks
 int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint32_t *outW, uint32_t *outH);
 
@@ -133,8 +151,23 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
 // nothing to guard there).  Plan::inputFormat stays the submission's and Plan::ownedFormat follows the submission's own rule.  Where the
 // submission plans and its RGBA32F twin does not (a footprint only the half kernels' LDS planes hold), the setting is not applied.  UNORM
 // formats and OVRFSR_HDR_DOMAIN_LINEAR: the plan is what it has always been.
+// `gaze`: non-null plans a GAZE-CAPABLE plan (a gaze is set on either eye: ovrfsr_set_gaze; `cfg` is the effective configuration, the gazes
+// in proj_centre) -- the same plan in every field but the list and span offsets, laid out in per-eye regions (PlanFields::gazeCapable) --
+// and leaves the rasterised hidden-area maps there for reaim_pipeline.
 Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden = nullptr, int hdrDomain = OVRFSR_HDR_DOMAIN_LINEAR);
+                      const HiddenArea *hidden = nullptr, int hdrDomain = OVRFSR_HDR_DOMAIN_LINEAR, HiddenMaps *gaze = nullptr);
+
+// The re-aim step (header, "Eye-tracked foveation"): what becomes of `current` when only proj_centre moved -- `effective` is the configuration
+// `current` was planned from with the gazes of the moment in proj_centre, `hidden` what plan_pipeline left in `gaze`.  Pure; re-runs
+// mask_constants, classify_mask and steps 1-5 of the tile lists, never the mesh rasteriser, the footprints or the tap tables.
+//   Nothing   the mask centres are the current ones: *reaimed is not written
+//   InPlace   plan_pipeline(effective) differs from `current` in centre, maskMode, the lists, records and spans with their counts, nSkipped and
+//             listsShared only, and the new lists fit the regions: *reaimed is that plan without its tap tables (`current` keeps them), and,
+//             with `hostRecords` = false, without the records (the launch manager builds them on the device: tile_records_kernel)
+//   Rebuild   anything else would move -- maskLists and with it the form, tileLists or overlapOutside; whether every group of both eyes is
+//             inside the radius, which resolve_in_staging decides by; or `current` is not gaze-capable: plan afresh.  *reaimed is not written
+enum class Reaim { Nothing, InPlace, Rebuild };
+Reaim reaim_pipeline(const Plan &current, const ovrfsr_config &effective, const HiddenMaps &hidden, Plan *reaimed, bool hostRecords = true);
 
 // what depends on the destination the call names
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat);

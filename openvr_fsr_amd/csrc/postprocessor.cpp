@@ -1,6 +1,7 @@
 // postprocessor.cpp -- see postprocessor.hpp.  Reference: src/postprocess/PostProcessor.cpp.
 #include "postprocessor.hpp"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +46,7 @@ static bool inject_failure() { return g_fail_countdown > 0 && --g_fail_countdown
 static inline bool inject_failure() { return false; }
 #endif
 static inline hipError_t dev_malloc(void **p, size_t bytes) { return inject_failure() ? hipErrorOutOfMemory : hipMalloc(p, bytes); }
+static inline hipError_t host_malloc(void **p, size_t bytes) { return inject_failure() ? hipErrorOutOfMemory : hipHostMalloc(p, bytes, hipHostMallocDefault); }
 static inline hipError_t event_create(hipEvent_t *e, unsigned flags) { return inject_failure() ? hipErrorOutOfMemory : hipEventCreateWithFlags(e, flags); }
 static inline hipError_t stream_create(hipStream_t *s, int priority) { return inject_failure() ? hipErrorOutOfMemory : hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority); }
 
@@ -157,14 +159,63 @@ void PostProcessor::ResetKeeping(bool keepRetired)
     replan_ = false;
     plan_ = Plan{};             // nothing of a previous configuration survives: the next apply plans afresh
     for (DeviceBuffer *b : {&swizzled_, &resolved_, &upscaled_, &sharpened_, &hdrIn_, &hdrOut_}) b->release();
+    FreeTables();
+    for (ProfileQuery &q : queries_) q.pending = false;
+    lastQuery_ = -1;
+    // summedGpuTime / countedQueries survive a Reset in the reference (plain members, PostProcessor.h:81-82): kept
+}
+
+void PostProcessor::FreeTables()
+{
+    // (a staging slot may still be the source of a copy in flight: its event first)
+    for (int i = 0; i < kGazeSlots; ++i) {
+        if (gazeEvent_[i]) {
+            if (gazeSlotUsed_[i]) (void)hipEventSynchronize(gazeEvent_[i]);
+            (void)hipEventDestroy(gazeEvent_[i]);
+        }
+        gazeEvent_[i] = nullptr;
+        gazeSlotUsed_[i] = false;
+    }
+    gazeSlot_ = 0;
+    if (gazeStage_) (void)hipHostFree(gazeStage_);
+    gazeStage_ = nullptr;
+    hiddenMaps_ = HiddenMaps{};
     for (void *t : {(void *)nisCoefDev_, (void *)bilinDev_, (void *)tileListDev_})
         if (t) (void)hipFree(t);
     nisCoefDev_ = nullptr;
     bilinDev_ = nullptr;
     tileListDev_ = tileRecDev_ = spanRecDev_ = nullptr;
-    for (ProfileQuery &q : queries_) q.pending = false;
-    lastQuery_ = -1;
-    // summedGpuTime / countedQueries survive a Reset in the reference (plain members, PostProcessor.h:81-82): kept
+}
+
+// ---- eye-tracked foveation (header).  The setters store the value and nothing else: no reset, no recorded eye dropped, a disabled ctx stays
+// disabled; the apply that launches the eye reads it (EnsurePlanned -> AimGaze).
+void PostProcessor::SetGaze(int eye, float x, float y)
+{
+    gazeSet_[eye & 1] = true;
+    gaze_[eye & 1][0] = x; gaze_[eye & 1][1] = y;
+    gazeMoved_ = true;
+}
+
+void PostProcessor::ClearGaze(int eye)
+{
+    gazeMoved_ = gazeMoved_ || gazeSet_[eye & 1];
+    gazeSet_[eye & 1] = false;
+}
+
+void PostProcessor::GetGaze(int eye, float xy[2], int *isSet) const
+{
+    const int e = eye & 1;
+    xy[0] = gazeSet_[e] ? gaze_[e][0] : cfg_.proj_centre[2 * e];
+    xy[1] = gazeSet_[e] ? gaze_[e][1] : cfg_.proj_centre[2 * e + 1];
+    *isSet = gazeSet_[e] ? 1 : 0;
+}
+
+ovrfsr_config PostProcessor::EffectiveConfig() const
+{
+    ovrfsr_config c = cfg_;
+    for (int e = 0; e < 2; ++e)
+        if (gazeSet_[e]) { c.proj_centre[2 * e] = gaze_[e][0]; c.proj_centre[2 * e + 1] = gaze_[e][1]; }
+    return c;
 }
 
 int PostProcessor::SetConfig(const ovrfsr_config &cfg)
@@ -238,6 +289,93 @@ int PostProcessor::EnsureBuffer(DeviceBuffer &buf, size_t need)
     return OVRFSR_OK;
 }
 
+// The tile lists of a gaze-capable plan: the device tables sized by the plan's regions, the staging ring and its events (created here, at
+// build time, so that a re-aim creates nothing), then the first upload the way every later one goes -- through a staging slot on the caller's
+// stream, the records built behind it by tile_records_kernel.
+int PostProcessor::BuildGazeTables(hipStream_t stream)
+{
+    const size_t listDwords = 2 * plan_.listRegion, spanDwords = 4 * plan_.spanRegion; // (listRegion is a multiple of 4: the records are 16-byte aligned)
+    hipError_t e = dev_malloc(reinterpret_cast<void **>(&tileListDev_), (5 * listDwords + spanDwords) * sizeof(uint32_t));
+    if (e != hipSuccess) return BuildFailed(e, "tile lists: ");
+    tileRecDev_ = tileListDev_ + listDwords;
+    spanRecDev_ = spanDwords ? tileRecDev_ + 4 * listDwords : nullptr;
+    e = host_malloc(reinterpret_cast<void **>(&gazeStage_), kGazeSlots * GazeSlotDwords() * sizeof(uint32_t));
+    for (int i = 0; i < kGazeSlots && e == hipSuccess; ++i) e = event_create(&gazeEvent_[i], hipEventDisableTiming);
+    if (e != hipSuccess) return BuildFailed(e, "gaze staging ring: ");
+    const int rc = UploadGazeLists(plan_, stream);
+    for (std::vector<uint32_t> *v : {&plan_.lists, &plan_.recs, &plan_.spans}) std::vector<uint32_t>().swap(*v);
+    return rc;
+}
+
+// `from`: a gaze-capable plan's lists and spans in its regions, with the counts and offsets plan_ has by now.  What each eye's region uses
+// goes into the next staging slot -- after the event behind that slot's last copies: a host wait only where the ring is full -- and from
+// there to the device on the caller's stream; then the records of those entries.  Nothing is allocated, nothing blocks.
+int PostProcessor::UploadGazeLists(const Plan &from, hipStream_t stream)
+{
+    const int slot = gazeSlot_;
+    gazeSlot_ = (slot + 1) % kGazeSlots;
+    hipError_t e = gazeSlotUsed_[slot] ? hipEventSynchronize(gazeEvent_[slot]) : hipSuccess;
+    uint32_t *host = gazeStage_ + (size_t)slot * GazeSlotDwords(), *hostSpans = host + 2 * plan_.listRegion;
+    uint32_t *hostRecs = hostSpans + 4 * plan_.spanRegion; // (kGazeHostRecords only)
+    TileRecordsArgs ta;
+    ta.lists = tileListDev_; ta.recs = tileRecDev_;
+    ta.bilX = bilinDev_; ta.bilY = bilinDev_ + plan_.tapYOff;
+    ta.g = record_grid(plan_);
+    ta.regionEntries = (uint32_t)plan_.listRegion;
+    for (int eye = 0; eye < 2 && e == hipSuccess; ++eye) {
+        const size_t base = (size_t)eye * plan_.listRegion; // == listOffInside[eye]
+        const size_t end = std::max(std::max(plan_.listOffRing[eye] + plan_.nRing[eye], plan_.listOffOutside[eye] + plan_.nOutside[eye]),
+                                    plan_.listOffRcas[eye] + plan_.nRcas[eye]);
+        const size_t n = ta.n[eye] = (uint32_t)(end - base);
+        if (n) {
+            std::memcpy(host + base, from.lists.data() + base, n * sizeof(uint32_t));
+            e = hipMemcpyAsync(tileListDev_ + base, host + base, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        }
+        if (kGazeHostRecords && n && e == hipSuccess) {
+            std::memcpy(hostRecs + 4 * base, from.recs.data() + 4 * base, 4 * n * sizeof(uint32_t));
+            e = hipMemcpyAsync(tileRecDev_ + 4 * base, hostRecs + 4 * base, 4 * n * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        }
+        const size_t sBase = 2 * plan_.spanOff[eye], sN = 2 * (size_t)plan_.nSpans[eye];
+        if (sN && e == hipSuccess) {
+            std::memcpy(hostSpans + sBase, from.spans.data() + sBase, sN * sizeof(uint32_t));
+            e = hipMemcpyAsync(spanRecDev_ + sBase, hostSpans + sBase, sN * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        }
+    }
+    if (e == hipSuccess) e = hipEventRecord(gazeEvent_[slot], stream);
+    gazeSlotUsed_[slot] = true;
+    if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("tile list upload: ") + hipGetErrorString(e));
+    return kGazeHostRecords ? OVRFSR_OK : Launched(launch_tile_records(ta, stream), "tile records");
+}
+
+// The gaze step of an apply (header, "Eye-tracked foveation"): a setter was called since the plan was aimed.  The planner's re-aim step says
+// what that means; nothing, new lists in place, or a rebuild -- of the tables only: the images the ctx owns, the recorded pair_submit eye and
+// the sequencer keep their place, since neither a size nor a format moves with a gaze.
+int PostProcessor::AimGaze(hipStream_t stream)
+{
+    Plan reaimed;
+    const Reaim aim = reaim_pipeline(plan_, EffectiveConfig(), hiddenMaps_, &reaimed, kGazeHostRecords);
+    if (aim != Reaim::Nothing && capturing_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, kCaptureRefusal); // (nothing touched: the gaze stays pending)
+    gazeMoved_ = false;
+    if (aim == Reaim::Nothing) return OVRFSR_OK;
+    int rc = OVRFSR_OK;
+    if (aim == Reaim::InPlace) {
+        static_cast<PlanFields &>(plan_) = reaimed;
+        if (plan_.tileLists) rc = UploadGazeLists(reaimed, stream);
+        if (rc == OVRFSR_OK) ++reaims_;
+    } else {
+        ovrfsr_image in = {};
+        in.width = plan_.inputWidth; in.height = plan_.inputHeight; in.format = plan_.inputFormat;
+        const bool onlyOneEye = plan_.onlyOneEye;
+        FreeTables();
+        initialized_ = false;
+        plan_ = Plan{};
+        rc = PrepareResources(in, onlyOneEye, stream);
+        if (rc == OVRFSR_OK) ++rebuilds_;
+    }
+    if (rc != OVRFSR_OK) enabled_ = false; // a failed (re)build disables the ctx until reset (:148-151)
+    return rc;
+}
+
 // The destination refusals that count as a failed build (exact stores: the sharpen stage's destination must be RGBA8 too): known only once
 // the call names its `out`, they disable the ctx.  The others (destination_refusal) are ApplyPostProcess's: a pair_submit first eye is
 // recorded with such a destination and refused when it is launched.
@@ -263,25 +401,38 @@ int PostProcessor::IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midS
 
 // Plan, then upload: everything that decides the pipeline -- and every refusal -- is host arithmetic (pipeline_plan.cpp), so a refused
 // configuration allocates nothing.  What the plan holds is then created on the device, in a fixed order (fault injection counts creations).
-int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneEye)
+int PostProcessor::BuildFailed(hipError_t e, const char *what)
+{
+    // (with a gaze in effect a (re)build that runs out of memory says so by its status: header, ovrfsr_set_gaze)
+    return Fail(plan_.gazeCapable && e == hipErrorOutOfMemory ? OVRFSR_ERR_OUT_OF_MEMORY : OVRFSR_ERR_HIP, std::string(what) + hipGetErrorString(e));
+}
+
+int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneEye, hipStream_t stream)
 {
     replan_ = false; // (asked for before anything was built: this is that plan)
     HiddenArea hidden;
     for (int eye = 0; eye < 2; ++eye) { hidden.uv[eye] = hiddenUv_[eye].data(); hidden.triangles[eye] = (uint32_t)(hiddenUv_[eye].size() / 6); }
-    const Refusal refused = plan_pipeline(cfg_, submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden, hdrDomain_);
+    // with a gaze set on either eye the plan is made from the gazes and laid out for re-aiming (Plan::gazeCapable); without one: as ever
+    const bool gazeCapable = gazeSet_[0] || gazeSet_[1];
+    gazeMoved_ = false; // (this plan is aimed at the gazes of the moment)
+    const Refusal refused = plan_pipeline(EffectiveConfig(), submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden, hdrDomain_,
+                                          gazeCapable ? &hiddenMaps_ : nullptr);
     if (refused) return Fail(refused.status, refused.text);
     if (plan_.useNis) { // coef_scale[512] | coef_usm[512], PostProcessor.cpp:366-382
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(nisCoefDev_, nis_coef_scale(), 512 * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(nisCoefDev_ + 512, nis_coef_usm(), 512 * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("NIS coefficient upload: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return BuildFailed(e, "NIS coefficient upload: ");
     }
     if (plan_.doUpscale) {
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&bilinDev_), plan_.taps.size() * sizeof(BilinTap));
         if (e == hipSuccess) e = hipMemcpy(bilinDev_, plan_.taps.data(), plan_.taps.size() * sizeof(BilinTap), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("bilinear tap tables: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return BuildFailed(e, "bilinear tap tables: ");
     }
-    if (plan_.tileLists) {
+    if (plan_.tileLists && plan_.gazeCapable) {
+        const int rc = BuildGazeTables(stream);
+        if (rc != OVRFSR_OK) return rc;
+    } else if (plan_.tileLists) {
         const std::vector<uint32_t> &lists = plan_.lists, &recs = plan_.recs, &spans = plan_.spans;
         const size_t listDwords = (lists.size() + 3) & ~(size_t)3; // the records follow the lists, 16-byte aligned
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&tileListDev_), (listDwords + recs.size() + spans.size()) * sizeof(uint32_t));
@@ -729,7 +880,10 @@ int PostProcessor::EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &i
     capturing_ = stream_capturing(stream);
     if (capturing_ && !PlannedFor(in, onlyOneEye, compareEyeLayout))
         return Fail(OVRFSR_ERR_INVALID_ARGUMENT, kCaptureRefusal); // (nothing touched: the capture stays valid, the ctx stays enabled)
-    int rc = recorded == Recorded::GoesFirst ? FlushPending(stream) : OVRFSR_OK;
+    // the gaze is read by the apply that launches the eye: in front of everything that launches, a recorded eye's flush included
+    int rc = OVRFSR_OK;
+    if (gazeMoved_ && initialized_ && !replan_ && (PlannedFor(in, onlyOneEye, compareEyeLayout) || sequence_.state().havePending)) rc = AimGaze(stream);
+    if (rc == OVRFSR_OK && recorded == Recorded::GoesFirst) rc = FlushPending(stream);
     if (rc != OVRFSR_OK) return rc;
     if (initialized_ && !PlannedFor(in, onlyOneEye, compareEyeLayout)) {
         bool retire = false; // the recorded eye belongs to the old resources
@@ -742,7 +896,7 @@ int PostProcessor::EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &i
         ResetKeeping(retire); // "Texture size changed, recreating resources" (:139-142)
     }
     if (!initialized_) {
-        rc = PrepareResources(in, onlyOneEye); // :146
+        rc = PrepareResources(in, onlyOneEye, stream); // :146
         if (rc != OVRFSR_OK) enabled_ = false; // :148-151
     }
     return rc;

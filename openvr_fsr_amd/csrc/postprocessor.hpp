@@ -47,6 +47,12 @@ public:
     // ovrfsr_set_hdr_domain / ovrfsr_get_hdr_domain behind their argument checks
     int SetHdrDomain(int domain);
     int HdrDomain() const { return hdrDomain_; }
+    // ovrfsr_set_gaze / ovrfsr_clear_gaze / ovrfsr_get_gaze / ovrfsr_gaze_stats behind their argument checks.  The setters store and nothing else:
+    // the apply that launches the eye reads the value (EnsurePlanned -> AimGaze)
+    void SetGaze(int eye, float x, float y);
+    void ClearGaze(int eye);
+    void GetGaze(int eye, float xy[2], int *isSet) const;
+    void GazeStats(uint32_t *reaims, uint32_t *rebuilds) const { *reaims = reaims_; *rebuilds = rebuilds_; }
     int LastGpuTimeMs(float *ms);
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
@@ -56,6 +62,13 @@ private:
     std::string lastError_;
     std::vector<float> hiddenUv_[2]; // the hidden-area mesh of each eye, 6 floats per triangle: outlives Reset and SetConfig (header)
     int hdrDomain_ = OVRFSR_HDR_DOMAIN_LINEAR; // ovrfsr_set_hdr_domain's value: outlives Reset and SetConfig too
+    // ovrfsr_set_gaze's values, per eye: they outlive Reset and SetConfig as well.  gazeMoved_: a setter was called since the plan was last
+    // aimed -- the next apply asks the planner's re-aim step what that means (nothing, new lists in place, or a rebuild) and counts the answer
+    bool gazeSet_[2] = {false, false};
+    float gaze_[2][2] = {{0, 0}, {0, 0}};
+    bool gazeMoved_ = false;
+    uint32_t reaims_ = 0, rebuilds_ = 0;
+    ovrfsr_config EffectiveConfig() const; // cfg_ with the gazes that are set in proj_centre: what the plan is made from
 
     // PostProcessor.h:16-24
     bool enabled_ = true;
@@ -73,6 +86,28 @@ private:
     uint32_t *tileListDev_ = nullptr;     // Plan::lists, then inside the same allocation:
     uint32_t *tileRecDev_ = nullptr;      //   Plan::recs, 4 dwords per list entry
     uint32_t *spanRecDev_ = nullptr;      //   Plan::spans, 2 dwords per segment
+    // A gaze-capable plan (Plan::gazeCapable): the same three tables laid out in the plan's per-eye regions, the records built on the device
+    // (tile_records_kernel), and what a re-aim needs to put new lists there without a host wait: the hidden-area maps the planner rasterised,
+    // and a ring of pinned staging slots, each a host image of the lists and spans (lists | spans, the device layout), each guarded by an
+    // event that is recorded behind its copies and waited on before the slot is written again
+    static constexpr int kGazeSlots = 4;
+    HiddenMaps hiddenMaps_;
+    uint32_t *gazeStage_ = nullptr;       // kGazeSlots x GazeSlotDwords() dwords of pinned host memory
+    hipEvent_t gazeEvent_[kGazeSlots] = {};
+    bool gazeSlotUsed_[kGazeSlots] = {};
+    int gazeSlot_ = 0;
+#ifdef OVRFSR_GAZE_HOST_RECORDS /* measurement build (never shipped): the records built on the host and uploaded behind the lists, no
+                                  tile_records_kernel -- the other side of the comparison in profiles/gaze.txt */
+    static constexpr bool kGazeHostRecords = true;
+#else
+    static constexpr bool kGazeHostRecords = false;
+#endif
+    size_t GazeSlotDwords() const { return (kGazeHostRecords ? 10 : 2) * plan_.listRegion + 4 * plan_.spanRegion; }
+    void FreeTables();                    // the plan's tables on the device and the staging ring
+    int BuildFailed(hipError_t e, const char *what); // a creation or upload of PrepareResources failed
+    int BuildGazeTables(hipStream_t stream);          // PrepareResources' part for the tile lists of a gaze-capable plan
+    int UploadGazeLists(const Plan &from, hipStream_t stream); // lists and spans through the next staging slot, then the records
+    int AimGaze(hipStream_t stream);      // EnsurePlanned's gaze step: nothing, a re-aim in place, or a rebuild of the tables
     // the memory-bound outside-tile kernel and the VALU-bound inside-tile kernel are independent: the former runs on
     // a ctx-owned auxiliary stream, forked from and joined back into the caller's stream with events
     hipStream_t auxStream_ = nullptr;
@@ -115,7 +150,7 @@ private:
 
     int Fail(int status, const std::string &what);
     int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled / R11G11B10F
-    int PrepareResources(const ovrfsr_image &in, bool onlyOneEye);        // :498-561: plan (pipeline_plan.h), then upload
+    int PrepareResources(const ovrfsr_image &in, bool onlyOneEye, hipStream_t stream); // :498-561: plan (pipeline_plan.h), then upload
     // one masked launch round: images first, first + step, ... (cnt of them) of the batch, all of eye `eye` when `split`
     struct EyePass {
         int eye; uint32_t cnt, first, step; bool split;

@@ -143,6 +143,31 @@ class PostProcessor:
         self._check(self._lib.ovrfsr_get_hdr_domain(self._ctx, C.byref(d)))
         return d.value
 
+    def set_gaze(self, eye, x, y):
+        """ovrfsr_set_gaze: the centre of one eye's sharp disc, in proj_centre's convention ([0,1] of that eye's image, y = 0 the first stored
+        row; accepted in [-1, 2]).  Stored only: the next apply that launches the eye re-aims the mask, in place where it can."""
+        self._check_arg(self._lib.ovrfsr_set_gaze(self._ctx, int(eye), float(x), float(y)), "ovrfsr_set_gaze")
+
+    def clear_gaze(self, eye):
+        """ovrfsr_clear_gaze: the eye's mask centre is cfg.proj_centre's again."""
+        self._check_arg(self._lib.ovrfsr_clear_gaze(self._ctx, int(eye)), "ovrfsr_clear_gaze")
+
+    def gaze(self, eye):
+        """ovrfsr_get_gaze: ((x, y), is_set) -- the eye's cfg.proj_centre where no gaze is set."""
+        xy, is_set = (C.c_float * 2)(), C.c_int()
+        self._check_arg(self._lib.ovrfsr_get_gaze(self._ctx, int(eye), xy, C.byref(is_set)), "ovrfsr_get_gaze")
+        return (xy[0], xy[1]), bool(is_set.value)
+
+    def gaze_stats(self):
+        """ovrfsr_gaze_stats: (re-aims in place, rebuilds) applies performed because of a gaze."""
+        reaims, rebuilds = C.c_uint32(), C.c_uint32()
+        self._check_arg(self._lib.ovrfsr_gaze_stats(self._ctx, C.byref(reaims), C.byref(rebuilds)), "ovrfsr_gaze_stats")
+        return reaims.value, rebuilds.value
+
+    def _check_arg(self, rc, what):
+        if rc != 0:  # (an argument check of the C ABI: it leaves ovrfsr_last_error alone)
+            raise K.OvrFsrError(rc, what)
+
     def last_gpu_time_ms(self):
         ms = C.c_float()
         self._check(self._lib.ovrfsr_last_gpu_time_ms(self._ctx, C.byref(ms)))
