@@ -468,6 +468,11 @@ OVRFSR_API int ovrfsr_hdr_map(const float *rgb_in, float *rgb_out, size_t n, int
  * the centre and nothing else.  No ABI version and no config field changes with these: a host probes for the symbols.
  *
  * x, y: proj_centre's convention and range -- [0, 1] of ONE eye's image, y = 0 at the first stored row, accepted in [-1, 2].
+ * Outside [0, 1] the centre is what ovrfsr_mask_constants makes of it: a negative coordinate is the coordinate 0 (the float -> uint store
+ * saturates; the reference's cast is undefined there), one above 1 puts the centre behind the image's edge -- a sliver of the disc on the
+ * image, or none of it: every pixel is then the bilinear fallback.  On a shared side-by-side texture a left gaze above 1 lands in the right
+ * half.  Groups are inside or outside by the reference's per-group rule on the groups it dispatches, at every such centre
+ * (tests/test_mask_edges.py, tests/test_gpu_mask_edges.py).
  *
  * THE RULE.  With a gaze set for eye e, every call behaves as the same call on a fresh ctx whose cfg.proj_centre holds the gaze in eye e's
  * two slots (the two centres of a shared side-by-side texture go through ovrfsr_mask_constants as they do today): status, error text,

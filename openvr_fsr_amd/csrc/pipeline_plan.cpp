@@ -305,7 +305,11 @@ HiddenMaps hidden_maps(const Plan &p, const HiddenArea &mesh)
 
 // Step 1.  `hidden` (empty: none) takes its tiles out first.  `byRadius` = false (no mixed mask: the lists exist for the mesh alone): every
 // other tile is an "inside" tile, whatever the radius -- the kernel that runs on it is the one the launch without lists runs, mask test included.
-TileClasses classify_tiles(const TileGrid &g, const uint32_t centre[4], uint32_t r2, bool byRadius, const std::vector<uint8_t> &hidden)
+// Only the groups the reference dispatches count, ceil(outW / groupW) x ceil(outH / groupH) of them: a partial last tile may hold a group
+// column or row that starts behind the image, and with the disc's centre behind that edge too such a group is nearer to it than the tile's
+// real ones -- testing it called tiles inside whose every pixel is outside.
+TileClasses classify_tiles(const TileGrid &g, uint32_t outW, uint32_t outH, const uint32_t centre[4], uint32_t r2, bool byRadius,
+                           const std::vector<uint8_t> &hidden)
 {
     const uint32_t gpx = g.tileW / g.groupW, gpy = g.tileH / g.groupH; // mask groups per tile
     TileClasses c;
@@ -315,6 +319,7 @@ TileClasses classify_tiles(const TileGrid &g, const uint32_t centre[4], uint32_t
         bool any = !byRadius;
         for (uint32_t k = 0; k < gpx * gpy && !any; ++k) {
             const uint32_t gx = gpx * txi + (k % gpx), gy = gpy * tyi + (k / gpx);
+            if (gx * g.groupW >= outW || gy * g.groupH >= outH) continue;
             const uint32_t cx = gx * g.groupW + g.groupW / 2, cy = gy * g.groupH + g.groupH / 2;
             const uint32_t ax = centre[0] - cx, ay = centre[1] - cy, bx = centre[2] - cx, by = centre[3] - cy;
             any = (ax * ax + ay * ay <= r2) || (bx * bx + by * by <= r2);
@@ -457,7 +462,7 @@ void tile_lists(Plan &p, const HiddenMaps &hidden, const Plan *tables)
     std::vector<uint32_t> ring[2];
     for (int eye = 0; eye < 2; ++eye) {
         if (p.gazeCapable) { p.lists.resize((size_t)eye * p.listRegion, 0u); p.spans.resize(2 * (size_t)eye * p.spanRegion, 0u); }
-        c[eye] = classify_tiles(g, p.centre[eye], p.radius[1], p.maskLists, hidden.eye[eye]);
+        c[eye] = classify_tiles(g, p.outputWidth, p.outputHeight, p.centre[eye], p.radius[1], p.maskLists, hidden.eye[eye]);
         const std::vector<uint32_t> rcas = rcas_tiles(c[eye], rcasOwnList);
         ring[eye] = ring_tiles(g, rcas, ring_candidates(c[eye], rcasOwnList, p.hiddenArea && p.form == Form::MaskSorted));
         if (cutSpans) rcas_spans(g, p.outputWidth, rcas, p.spans, &p.spanOff[eye], &p.nSpans[eye]);

@@ -8,6 +8,7 @@
 //     "no_mesh_equal"   the plan of the six-argument call and the plan of the call with an EMPTY mesh, serialised by value (plan_serial.h), are equal
 //     "form", "form_plain"   the form with the mesh and of the six-argument call
 //     "tile_lists", "hidden_area", "lists_shared", "tiles", "tile" [w, h], "skipped" [l, r]
+//     "mask_mode" [l, r]   the plan's maskMode per eye (0 all inside, 1 all outside, 2 mixed), "centre" per eye the four mask centres
 //     "inside", "ring", "outside", "rcas"   per eye, the tile indices of each list segment as the plan holds them
 //     "spans"           per eye, [x0, tileRow, xEnd] of every RCAS segment
 //     "hidden"          per eye, the tile map the rule gives for the planned output size (hidden_tiles), row-major
@@ -85,6 +86,8 @@ int main(int argc, char **argv)
             std::printf(", \"form\": \"%s\", \"form_plain\": \"%s\", \"out\": [%u, %u], \"tile_lists\": %d, \"hidden_area\": %d, \"lists_shared\": %d, "
                         "\"tiles\": %u, \"tile\": [%u, %u], \"skipped\": [%u, %u]", form_name(p.form), form_name(plain.form), p.outputWidth, p.outputHeight,
                         (int)p.tileLists, (int)p.hiddenArea, (int)p.listsShared, tx * ty, tw, th, p.nSkipped[0], p.nSkipped[1]);
+            std::printf(", \"mask_mode\": [%u, %u], \"centre\": [[%u, %u, %u, %u], [%u, %u, %u, %u]]", p.maskMode[0], p.maskMode[1], p.centre[0][0],
+                        p.centre[0][1], p.centre[0][2], p.centre[0][3], p.centre[1][0], p.centre[1][1], p.centre[1][2], p.centre[1][3]);
             print_list("inside", p, p.listOffInside, p.nInside);
             print_list("ring", p, p.listOffRing, p.nRing);
             print_list("outside", p, p.listOffOutside, p.nOutside);
