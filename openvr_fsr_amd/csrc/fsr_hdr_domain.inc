@@ -112,13 +112,12 @@ hipError_t launch_hdr_forward(int fmt, const uint8_t *src, uint32_t srcPitch, ui
                               uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    const uint32_t vec = ((uintptr_t)src % 16u == 0 && srcPitch % 16u == 0 && (batch < 2 || srcStride % 16u == 0)) ? 1u : 0u;
+    const uint32_t vec = rows_vectorizable(src, srcPitch, srcStride, batch, 16u);
     if (fmt == FMT_RGBA16F)
-        hipLaunchKernelGGL((ovrfsr_fast::hdr_forward_kernel<FMT_RGBA16F>), dim3((w + 511u) / 512u, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h, vec);
-    else if (fmt == FMT_RGBA32F)
-        hipLaunchKernelGGL((ovrfsr_fast::hdr_forward_kernel<FMT_RGBA32F>), dim3((w + 255u) / 256u, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h, vec);
-    else return hipErrorInvalidValue; // not a float pipeline input: no kernel is built for it
-    return hipGetLastError();
+        return launch_kernel<ovrfsr_fast::hdr_forward_kernel<FMT_RGBA16F>>(dim3((w + 511u) / 512u, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h, vec);
+    if (fmt == FMT_RGBA32F)
+        return launch_kernel<ovrfsr_fast::hdr_forward_kernel<FMT_RGBA32F>>(dim3((w + 255u) / 256u, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h, vec);
+    return hipErrorInvalidValue; // not a float pipeline input: no kernel is built for it
 }
 
 // src: batch images of w x h RGBA32F texels, tight; image i of the destination at dst + i * dstStride
@@ -126,15 +125,14 @@ hipError_t launch_hdr_back(int fmt, const uint8_t *src, uint8_t *dst, uint32_t d
                            uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    const uint32_t vec = ((uintptr_t)dst % 16u == 0 && dstPitch % 16u == 0 && (batch < 2 || dstStride % 16u == 0)) ? 1u : 0u;
+    const uint32_t vec = rows_vectorizable(dst, dstPitch, dstStride, batch, 16u);
     if (fmt == FMT_RGBA8)
-        hipLaunchKernelGGL((ovrfsr_fast::hdr_back_kernel<FMT_RGBA8>), dim3((w + 1023u) / 1024u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
-    else if (fmt == FMT_RGBA16F)
-        hipLaunchKernelGGL((ovrfsr_fast::hdr_back_kernel<FMT_RGBA16F>), dim3((w + 511u) / 512u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
-    else if (fmt == FMT_RGBA32F)
-        hipLaunchKernelGGL((ovrfsr_fast::hdr_back_kernel<FMT_RGBA32F>), dim3((w + 255u) / 256u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
-    else return hipErrorInvalidValue; // (RGB10A2 is no destination of a float pipeline: destination_refusal)
-    return hipGetLastError();
+        return launch_kernel<ovrfsr_fast::hdr_back_kernel<FMT_RGBA8>>(dim3((w + 1023u) / 1024u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
+    if (fmt == FMT_RGBA16F)
+        return launch_kernel<ovrfsr_fast::hdr_back_kernel<FMT_RGBA16F>>(dim3((w + 511u) / 512u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
+    if (fmt == FMT_RGBA32F)
+        return launch_kernel<ovrfsr_fast::hdr_back_kernel<FMT_RGBA32F>>(dim3((w + 255u) / 256u, h, batch), dim3(256), 0, s, src, dst, dstPitch, dstStride, w, h, vec);
+    return hipErrorInvalidValue; // (RGB10A2 is no destination of a float pipeline: destination_refusal)
 }
 
 } // namespace ovrfsr

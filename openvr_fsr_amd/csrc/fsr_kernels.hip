@@ -201,37 +201,24 @@ __global__ __launch_bounds__(256) void packed_resolve_kernel(const uint8_t *__re
 } // namespace ovrfsr_fast
 #pragma clang fp contract(on)
 
-namespace ovrfsr {
+// The launchers.  fsr_launch_impl.h holds what they share with the other kernel units; here, and in that header, a kernel is emitted
+// where a launcher first names it: the order of the launch_* definitions below, of the two includes between them and of the branches
+// inside every launcher IS the order of the kernels in the code object.  The byte comparison of the code objects against the parent
+// commit's (profiles/launch_layer.txt) holds it; that is the only reason launch_easu and launch_rcas stand behind the includes.
+#define OVRFSR_LAUNCH_FSR 1
+#include "fsr_launch_impl.h"
 
-template <int I, int O, bool M>
-static void easu_fast_go(int pitch, const EasuArgs &a, dim3 grid, hipStream_t s)
-{
-    const size_t lds = (size_t)pitch * a.cellsH * 36 + (size_t)pitch * kLumPadRows * 4; // colour + analysis (float4) + luma planes + pad rows
-    if (pitch == 28) hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 28, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    else if (pitch == 32) hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 32, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    else hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 40, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-}
+namespace ovrfsr {
 
 template <int I, int O>
 static hipError_t easu_go(bool strict, const EasuArgs &a, dim3 grid, size_t lds, hipStream_t s)
 {
     const int pitch = easu_kernel_pitch(a.cellsW);
-    const bool masked = a.m.mode[0] != MASK_ALL_INSIDE || a.m.mode[1] != MASK_ALL_INSIDE;
-    if (strict) hipLaunchKernelGGL((ovrfsr_strict::easu_kernel<I, O>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
+    if (strict) return launch_kernel<ovrfsr_strict::easu_kernel<I, O>>(grid, dim3(kThreads), lds, s, a);
     // footprints wider than the fixed pitches, and the 10-bit format (a quantised destination without a near-tie guard of
     // its own): the generic kernel, whose resolve is the reference-order one in every build
-    else if (pitch == 0 || I == FMT_RGB10A2 || O == FMT_RGB10A2) hipLaunchKernelGGL((ovrfsr_fast::easu_kernel<I, O>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    else if (masked) easu_fast_go<I, O, true>(pitch, a, grid, s);
-    else easu_fast_go<I, O, false>(pitch, a, grid, s);
-    return hipGetLastError();
-}
-// rcas_dpp_kernel's height for an unmasked launch of `batch` images (see rcas_go): true = the 16-row form
-static bool rcas_dpp_small(const RcasArgs &a, uint32_t batch)
-{
-    const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
-    const uint64_t wgs = (uint64_t)tx * ty * batch;
-    const uint64_t full = (wgs + kRcasResident - 1) / kRcasResident, half = (2 * wgs + kRcasResident - 1) / kRcasResident;
-    return wgs < 16 * kRcasResident && 103 * half < 200 * full;
+    if (pitch == 0 || I == FMT_RGB10A2 || O == FMT_RGB10A2) return launch_kernel<ovrfsr_fast::easu_kernel<I, O>>(grid, dim3(kThreads), lds, s, a);
+    return is_masked(a.m) ? easu_fast_go<I, O, true>(pitch, a, grid, s) : easu_fast_go<I, O, false>(pitch, a, grid, s);
 }
 
 // The fast RCAS kernels of an RGBA8 source, as two sets with the same three members: the plain instances by destination format, and the
@@ -247,29 +234,19 @@ struct RcasExactSet {
 };
 
 // The form of a fast RCAS launch from an RGBA8 image, one rule for both sets: the DPP kernel on whole rows of 32- or 16-row workgroups
-// (unmasked), on the span records of a mask-sorted launch, or the per-lane-loads kernel on `grid`.
+// (unmasked: rcas_dpp_small, fsr_sizes.h), on the span records of a mask-sorted launch, or the per-lane-loads kernel on `grid`.
 template <class Set>
-static void rcas_fast_go(bool dpp, const RcasArgs &a, dim3 grid, hipStream_t s)
+static hipError_t rcas_fast_go(bool dpp, const RcasArgs &a, dim3 grid, hipStream_t s)
 {
-    const bool unmasked = !a.tileList && a.m.mode[0] == MASK_ALL_INSIDE && a.m.mode[1] == MASK_ALL_INSIDE;
-    if (dpp && unmasked) {
-        const uint32_t tx = (uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW, ty = (uint32_t)(a.v.outH + kRcasDppTileH - 1) / kRcasDppTileH;
-        // small launches: the grid is r = workgroups / kRcasResident rounds of the resident workgroups, the last one partly filled;
-        // half-height workgroups run ceil(2r) rounds of half the length (3 % more work per pixel).  One C2 eye image: r = 1.41,
-        // 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us, profiles/r05_frame.txt); a batch: no difference, the
-        // 8-row form wins
-        if (rcas_dpp_small(a, grid.z)) {
-            const uint32_t ty16 = (uint32_t)(a.v.outH + 15) / 16;
-            hipLaunchKernelGGL((Set::template dpp<false, 16>()), dim3(tx * ty16, 1, grid.z), dim3(kThreads), 0, s, a);
-        } else {
-            hipLaunchKernelGGL((Set::template dpp<false, kRcasDppTileH>()), dim3(tx * ty, 1, grid.z), dim3(kThreads), 0, s, a);
-        }
-    } else if (dpp && a.tileList && a.spanRec && a.nSpans) {
-        // mask-sorted form: the DPP kernel on 62-column segments of the runs of tiles touching the radius
-        hipLaunchKernelGGL((Set::template dpp<true, kRcasDppTileH>()), dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((Set::direct()), grid, dim3(kThreads), 0, s, a);
+    if (dpp && !a.tileList && !is_masked(a.m)) {
+        const uint32_t tx = rcas_dpp_tiles_x(a.v.outW);
+        if (rcas_dpp_small(a.v.outW, a.v.outH, grid.z))
+            return launch_kernel<*Set::template dpp<false, 16>()>(dim3(tx * rcas_dpp_tiles_y(a.v.outH, 16), 1, grid.z), dim3(kThreads), 0, s, a);
+        return launch_kernel<*Set::template dpp<false, kRcasDppTileH>()>(dim3(tx * rcas_dpp_tiles_y(a.v.outH, kRcasDppTileH), 1, grid.z), dim3(kThreads), 0, s, a);
     }
+    // mask-sorted form: the DPP kernel on 62-column segments of the runs of tiles touching the radius
+    if (dpp && a.tileList && a.spanRec && a.nSpans) return launch_kernel<*Set::template dpp<true, kRcasDppTileH>()>(dim3(a.nSpans, 1, grid.z), dim3(kThreads), 0, s, a);
+    return launch_kernel<*Set::direct()>(grid, dim3(kThreads), 0, s, a);
 }
 
 template <int I, int O>
@@ -280,99 +257,49 @@ static hipError_t rcas_go(bool strict, bool exact, const RcasArgs &a, dim3 grid,
 #else
     constexpr bool dpp = true;
 #endif
-    if (strict) {
-        hipLaunchKernelGGL((ovrfsr_strict::rcas_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
-    } else if (exact) {
+    if (strict) return launch_kernel<ovrfsr_strict::rcas_kernel<I, O>>(grid, dim3(kThreads), 0, s, a);
+    if (exact) {
         // exact stores: the guarded RGBA8 -> RGBA8 instances; no other pair has any
-        if constexpr (I == FMT_RGBA8 && O == FMT_RGBA8) rcas_fast_go<RcasExactSet>(true, a, grid, s);
+        if constexpr (I == FMT_RGBA8 && O == FMT_RGBA8) return rcas_fast_go<RcasExactSet>(true, a, grid, s);
         else return hipErrorInvalidValue;
-    } else if constexpr (I == FMT_RGBA8 && O != FMT_RGB10A2) {
-        rcas_fast_go<RcasPlainSet<O>>(dpp, a, grid, s);
-    } else {
-        hipLaunchKernelGGL((ovrfsr_fast::rcas_direct_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
     }
-    return hipGetLastError();
+    if constexpr (I == FMT_RGBA8 && O != FMT_RGB10A2) return rcas_fast_go<RcasPlainSet<O>>(dpp, a, grid, s);
+    else return launch_kernel<ovrfsr_fast::rcas_direct_kernel<I, O>>(grid, dim3(kThreads), 0, s, a);
 }
 
+// (which intermediates a source has, and the dynamic-LDS cap: mid_reachable, launch_kernel_big_lds, fsr_launch_impl.h)
 template <int I, int M, int O>
-static hipError_t fused_go3(bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
-{
-    const int pitch = easu_fast_pitch(a.cellsW);
-    // the EASU planes plus the 34x34 intermediate can exceed the 64 KiB default cap on dynamic LDS (160 KiB per CU).  The
-    // attribute is per DEVICE (a one-process node driver holds one ctx per device, examples/bench_node.c): latched per
-    // (kernel instantiation, device), one bit per device ordinal.
-    auto raise = [](const void *fn, std::atomic<uint64_t> &done) -> hipError_t {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsMax);
-        if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
-        return e;
-    };
-    if (strict) {
-        static std::atomic<uint64_t> done{0};
-        const hipError_t e = raise(reinterpret_cast<const void *>(&ovrfsr_strict::fused_kernel<I, M, O, 0>), done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ovrfsr_strict::fused_kernel<I, M, O, 0>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    } else if (pitch == 32) {
-        static std::atomic<uint64_t> done{0};
-        const hipError_t e = raise(reinterpret_cast<const void *>(&ovrfsr_fast::fused_kernel<I, M, O, 32, kFusedThreads>), done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ovrfsr_fast::fused_kernel<I, M, O, 32, kFusedThreads>), grid, dim3(kFusedThreads), lds, s, with_lds(a, lds));
-    } else if (pitch == 40) {
-        static std::atomic<uint64_t> done{0};
-        const hipError_t e = raise(reinterpret_cast<const void *>(&ovrfsr_fast::fused_kernel<I, M, O, 40, kFusedThreads>), done);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ovrfsr_fast::fused_kernel<I, M, O, 40, kFusedThreads>), grid, dim3(kFusedThreads), lds, s, with_lds(a, lds));
-    } else {
-        return hipErrorInvalidValue;
+struct FusedAny {
+    static hipError_t go(bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
+    {
+        if (strict) return launch_kernel_big_lds<ovrfsr_strict::fused_kernel<I, M, O, 0>>(grid, dim3(kThreads), lds, s, a);
+        return FusedFast<I, M, O>::go(a, grid, lds, s);
     }
-    return hipGetLastError();
-}
-// The intermediate has the pipeline input's format (R8G8B8A8 -> UNORM8, RGBA16F -> half: PostProcessor::IntermediateFormat with
-// cfg.reference_formats = 0, this library's own rule) or, with quantize_intermediate = 0, stays in float: those are the only (input,
-// intermediate) pairs a ctx asks the FUSED kernel for, so only they are instantiated (12 of the 27 format triples of the fused and
-// outside-tile kernels were dead weight in the library until round 4).  Under cfg.reference_formats = 1 (DetermineOutputFormat,
-// PostProcessor.cpp:63-74) a float input has a UNORM8 intermediate: a ctx then asks for (RGBA16F | RGBA32F, RGBA8) too, of the
-// outside-tile kernel only (easu_outside_go) -- the fused kernel is refused for that pair at (re)build, none is built.
-template <int I, int M> constexpr bool mid_reachable() { return M == I || M == FMT_RGBA32F; }
-template <int I, int M> constexpr bool mid_reachable_outside() { return mid_reachable<I, M>() || (M == FMT_RGBA8 && (I == FMT_RGBA16F || I == FMT_RGBA32F)); }
-
+};
 template <int I, int O>
-static hipError_t fused_go(int mid_fmt, bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
+static hipError_t fused_any_go(int mid_fmt, bool strict, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
 {
-    if (mid_fmt == (int)I) return fused_go3<I, I, O>(strict, a, grid, lds, s);
-    if (mid_fmt == FMT_RGBA32F) return fused_go3<I, FMT_RGBA32F, O>(strict, a, grid, lds, s);
-    return hipErrorInvalidValue;
+    return fused_go<FusedAny, I, O, FMT_RGBA8, FMT_RGBA16F, FMT_RGBA32F>(mid_fmt, strict, a, grid, lds, s);
 }
 
 hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const FusedArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)
 {
     launch_fresh();
-    FusedArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const FusedArgs a = prepared(a_in);
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
     const bool strict = prec == PREC_FP32_STRICT;
     if (!strict && easu_fast_pitch(a.cellsW) == 0) return hipErrorInvalidValue;
-    const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
+    const dim3 grid = tile_grid(a, nTiles, batch);
     const size_t lds = fused_lds_bytes(prec, in_fmt, mid_fmt, a.cellsW, a.cellsH);
     if (lds > kFusedLdsMax) return hipErrorInvalidValue; // never launch with less LDS than the plane layout assumes (callers pre-check: PrepareResources)
     if (in_fmt == FMT_R11G11B10F) return strict ? hipErrorInvalidValue : launch_fused_packed(mid_fmt, out_fmt, a, grid, lds, s); // fsr_packed_kernels.hip
-    OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, fused_go, mid_fmt, strict, a, grid, lds, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_NO_TEN_BIT, fused_any_go, mid_fmt, strict, a, grid, lds, s)
 }
 
 template <int I, int O>
-static hipError_t easu_outside_go(int mid_fmt, const EasuArgs &a, dim3 grid, hipStream_t s)
+static hipError_t easu_outside_any(int mid_fmt, const EasuArgs &a, dim3 grid, hipStream_t s)
 {
-    if (mid_fmt < 0) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, -1>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == FMT_RGBA32F) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, FMT_RGBA32F>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == (int)I && I != FMT_RGB10A2) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, (I == FMT_RGB10A2 ? -1 : I)>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == FMT_RGBA8 && mid_reachable_outside<I, FMT_RGBA8>()) // a float source behind a UNORM8 intermediate (cfg.reference_formats)
-        hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, (mid_reachable_outside<I, FMT_RGBA8>() ? (int)FMT_RGBA8 : -1)>), grid, dim3(kThreads), 0, s, a);
-    else return hipErrorInvalidValue; // not an (input, intermediate) pair a ctx produces (see mid_reachable)
-    return hipGetLastError();
+    return easu_outside_go<I, O, -1, FMT_RGBA32F, FMT_RGBA16F, FMT_RGBA8>(mid_fmt, a, grid, s);
 }
 
 // nTiles blocks, each resolving tile a.tileList[block]: tiles entirely outside the radius (product build only).
@@ -381,7 +308,6 @@ static hipError_t easu_outside_go(int mid_fmt, const EasuArgs &a, dim3 grid, hip
 // LDS-staged outside-tile kernel (outside_staged_kernel): where outside_staged_ok (fsr_sizes.h) says so.
 // mid_fmt < 0: the EASU pass alone; >= 0: final pixel = tint(value read back from a mid_fmt intermediate), RGBA32F = tint
 // of the un-rounded value (also NIS DirectCopy, tileH = 24).
-
 template <int TH, int I, int O>
 static hipError_t outside_staged_go(int mid_fmt, const OutsideArgs &a, dim3 grid, hipStream_t s)
 {
@@ -389,16 +315,15 @@ static hipError_t outside_staged_go(int mid_fmt, const OutsideArgs &a, dim3 grid
     if constexpr (I != FMT_RGBA8) {
         return hipErrorInvalidValue;
     } else if constexpr (TH == 24) { // NIS DirectCopy
-        hipLaunchKernelGGL((ovrfsr_fast::outside_staged_kernel<24, I, O, FMT_RGBA32F>), grid, dim3(8 * 24), lds, s, with_lds(a, lds));
+        return launch_kernel<ovrfsr_fast::outside_staged_kernel<24, I, O, FMT_RGBA32F>>(grid, dim3(8 * 24), lds, s, a);
     } else {
         switch (mid_fmt) { // RGBA8 sources: a UNORM8 or a float intermediate, or the EASU pass alone
-        case FMT_RGBA8: hipLaunchKernelGGL((ovrfsr_fast::outside_staged_kernel<32, I, O, FMT_RGBA8>), grid, dim3(256), lds, s, with_lds(a, lds)); break;
-        case FMT_RGBA32F: hipLaunchKernelGGL((ovrfsr_fast::outside_staged_kernel<32, I, O, FMT_RGBA32F>), grid, dim3(256), lds, s, with_lds(a, lds)); break;
+        case FMT_RGBA8: return launch_kernel<ovrfsr_fast::outside_staged_kernel<32, I, O, FMT_RGBA8>>(grid, dim3(256), lds, s, a);
+        case FMT_RGBA32F: return launch_kernel<ovrfsr_fast::outside_staged_kernel<32, I, O, FMT_RGBA32F>>(grid, dim3(256), lds, s, a);
         case FMT_RGBA16F: return hipErrorInvalidValue;
-        default: hipLaunchKernelGGL((ovrfsr_fast::outside_staged_kernel<32, I, O, -1>), grid, dim3(256), lds, s, with_lds(a, lds)); break;
+        default: return launch_kernel<ovrfsr_fast::outside_staged_kernel<32, I, O, -1>>(grid, dim3(256), lds, s, a);
         }
     }
-    return hipGetLastError();
 }
 template <int I, int O> static hipError_t outside_staged_go32(int mid_fmt, const OutsideArgs &a, dim3 grid, hipStream_t s) { return outside_staged_go<32, I, O>(mid_fmt, a, grid, s); }
 template <int I, int O> static hipError_t outside_staged_go24(int mid_fmt, const OutsideArgs &a, dim3 grid, hipStream_t s) { return outside_staged_go<24, I, O>(mid_fmt, a, grid, s); }
@@ -406,8 +331,7 @@ template <int I, int O> static hipError_t outside_staged_go24(int mid_fmt, const
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a_in, uint32_t nTiles, uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    OutsideArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    OutsideArgs a = prepared(a_in);
     if (!a.tileList || !a.tileRec || !a.bilX || !a.bilY || nTiles == 0 || !outside_staged_ok(a.v, in_fmt)) return hipErrorInvalidValue;
     if (a.lds_cols < 2 || a.lds_cols > 36 || a.lds_rows < 2 || a.lds_rows > 34) return hipErrorInvalidValue;
     // persistent workgroups: block b walks list entries b, b + G, ... (G a multiple of 8: the list is XCD-banded, entry e
@@ -425,18 +349,13 @@ hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt
 hipError_t launch_easu_outside(int in_fmt, int mid_fmt, int out_fmt, const EasuArgs &a_in, uint32_t nTiles, uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    EasuArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const EasuArgs a = prepared(a_in);
     if (!a.tileList || nTiles == 0) return hipErrorInvalidValue;
-    if (a.bilX && a.bilY && a.tileRec && outside_staged_ok(a.v, in_fmt)) { // no records: the per-pixel kernel below needs none
-        OutsideArgs o;
-        o.v = a.v; o.tilesX = a.tilesX; o.tileList = a.tileList; o.tileRec = a.tileRec; o.bilX = a.bilX; o.bilY = a.bilY; o.debug = a.debug;
-        o.lds_cols = a.outsideCols; o.lds_rows = a.outsideRows;
-        return launch_outside_staged(kTileH, in_fmt, mid_fmt, out_fmt, o, nTiles, batch, s);
-    }
+    if (a.bilX && a.bilY && a.tileRec && outside_staged_ok(a.v, in_fmt)) // no records: the per-pixel kernel below needs none
+        return launch_outside_staged(kTileH, in_fmt, mid_fmt, out_fmt, outside_args(a, a.debug), nTiles, batch, s);
     const dim3 grid(nTiles, 1, batch);
     if (in_fmt == FMT_R11G11B10F) return launch_easu_outside_packed(mid_fmt, out_fmt, a, grid, s); // fsr_packed_kernels.hip
-    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_outside_go, mid_fmt, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_outside_any, mid_fmt, a, grid, s)
 }
 
 // B8G8R8A8 -> R8G8B8A8 into a tightly packed buffer (dst pitch = 4*w, image stride = 4*w*h): a byte shuffle, 16 texels
@@ -460,8 +379,7 @@ hipError_t launch_bgra_to_rgba(const uint8_t *src, uint32_t srcPitch, uint64_t s
                                uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    hipLaunchKernelGGL(bgra_to_rgba_kernel, dim3((w + 255) / 256, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h);
-    return hipGetLastError();
+    return launch_kernel<bgra_to_rgba_kernel>(dim3((w + 255) / 256, h, batch), dim3(256), 0, s, src, srcPitch, srcStride, dst, w, h);
 }
 
 // one launch of the resolve pass: what both resolve kernels take, and where they run
@@ -470,24 +388,25 @@ struct ResolveJob {
     dim3 grid; hipStream_t s;
 };
 template <int F, int S>
-static void resolve_launch(const ResolveJob &j)
+static hipError_t resolve_launch(const ResolveJob &j)
 {
     if constexpr (F == FMT_R11G11B10F)
-        hipLaunchKernelGGL((ovrfsr_fast::packed_resolve_kernel<S>), j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
+        return launch_kernel<ovrfsr_fast::packed_resolve_kernel<S>>(j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
     else
-        hipLaunchKernelGGL((ovrfsr_fast::resolve_kernel<F, S>), j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
+        return launch_kernel<ovrfsr_fast::resolve_kernel<F, S>>(j.grid, dim3(256), 0, j.s, j.src, j.srcPitch, j.srcStride, j.dst, j.dstPitch, j.w, j.h, j.vec);
 }
-// the kernel of the run-time sample count; false: no kernel is built for it (one sample: R11G11B10F only, which is unpacked whatever the count)
+// the kernel of the run-time sample count; none is built for any other (one sample: R11G11B10F only, which is unpacked whatever the count)
 template <int F>
-static bool resolve_go(int samples, const ResolveJob &j)
+static hipError_t resolve_go(int samples, const ResolveJob &j)
 {
     switch (samples) {
-    case 1: if constexpr (F == FMT_R11G11B10F) { resolve_launch<F, 1>(j); return true; } else return false;
-    case 2: resolve_launch<F, 2>(j); return true;
-    case 4: resolve_launch<F, 4>(j); return true;
-    case 8: resolve_launch<F, 8>(j); return true;
-    default: return false;
+    case 1: if constexpr (F == FMT_R11G11B10F) return resolve_launch<F, 1>(j); else break;
+    case 2: return resolve_launch<F, 2>(j);
+    case 4: return resolve_launch<F, 4>(j);
+    case 8: return resolve_launch<F, 8>(j);
+    default: break;
     }
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t srcPitch, uint64_t srcStride, uint8_t *dst, uint32_t w, uint32_t h,
@@ -497,29 +416,19 @@ hipError_t launch_resolve(int fmt, int samples, const uint8_t *src, uint32_t src
     // every thread writes 16 bytes: 16 / texel bytes texels, read from samples x 16 source bytes -- R11G11B10F (unpack, and resolve): two
     // texels, 8 x samples source bytes (one 8-byte load at one sample)
     const bool packed = fmt == FMT_R11G11B10F;
-    const uint32_t per = 256u * (packed ? 2u : 16u / texel_bytes((uint32_t)fmt)), al = packed && samples == 1 ? 8u : 16u;
-    const uint32_t vec = ((uintptr_t)src % al == 0 && srcPitch % al == 0 && (batch < 2 || srcStride % al == 0)) ? 1u : 0u;
+    const uint32_t per = 256u * (packed ? 2u : 16u / texel_bytes((uint32_t)fmt));
+    const uint32_t vec = rows_vectorizable(src, srcPitch, srcStride, batch, packed && samples == 1 ? 8u : 16u);
     const ResolveJob j{src, srcPitch, srcStride, dst, resolve_pitch(fmt, w), w, h, vec, dim3((w + per - 1) / per, h, batch), s};
-    bool launched = false; // stays false for a format or a sample count no kernel is built for
-    switch (fmt) {
-    case FMT_R11G11B10F: launched = resolve_go<FMT_R11G11B10F>(samples, j); break;
-    case FMT_RGBA8: launched = resolve_go<FMT_RGBA8>(samples, j); break;
-    case FMT_RGBA16F: launched = resolve_go<FMT_RGBA16F>(samples, j); break;
-    case FMT_RGBA32F: launched = resolve_go<FMT_RGBA32F>(samples, j); break;
-    case FMT_RGB10A2: launched = resolve_go<FMT_RGB10A2>(samples, j); break;
-    case FMT_BGRA8: launched = resolve_go<FMT_BGRA8>(samples, j); break;
-    default: break;
+    switch (fmt) { // (a format no kernel is built for: hipErrorInvalidValue)
+    case FMT_R11G11B10F: return resolve_go<FMT_R11G11B10F>(samples, j);
+    case FMT_RGBA8: return resolve_go<FMT_RGBA8>(samples, j);
+    case FMT_RGBA16F: return resolve_go<FMT_RGBA16F>(samples, j);
+    case FMT_RGBA32F: return resolve_go<FMT_RGBA32F>(samples, j);
+    case FMT_RGB10A2: return resolve_go<FMT_RGB10A2>(samples, j);
+    case FMT_BGRA8: return resolve_go<FMT_BGRA8>(samples, j);
+    default: return hipErrorInvalidValue;
     }
-    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
-
-} // namespace ovrfsr
-// The forward and back passes of OVRFSR_HDR_DOMAIN_SRTM with their launchers: a file of their own inside this unit (it opens its own
-// namespaces).  Here, in front of launch_rcas, so that the kernels launch_rcas instantiates stay the last ones of the code object.
-#include "fsr_hdr_domain.inc"
-// ... and the tile records of a gaze-capable ctx, built on the device (tile_records_kernel), likewise
-#include "fsr_tile_records.inc"
-namespace ovrfsr {
 
 #ifdef OVRFSR_BOUNDS
 // Drives the checked accessors through every kind of violation exactly once (tests/test_gpu_bounds.py asserts the counts): proof that a
@@ -570,14 +479,9 @@ hipError_t bounds_selftest() { return hipErrorNotSupported; }
 hipError_t tie_audit_read(unsigned long long out[6], bool reset)
 {
 #ifdef OVRFSR_TIE_AUDIT
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ovrfsr_tie_audit), 6 * sizeof(unsigned long long));
-    if (e == hipSuccess && reset) {
-        const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ovrfsr_tie_audit), z, sizeof z);
-    }
     // the instances that read R11G11B10F words count in their own translation unit: sums, and the larger of the two maxima
     unsigned long long p[6];
+    hipError_t e = read_counters(HIP_SYMBOL(g_ovrfsr_tie_audit), out, 6, reset);
     if (e == hipSuccess) e = tie_audit_read_packed(p, reset);
     if (e == hipSuccess)
         for (int i = 0; i < 6; ++i) out[i] = i < 4 ? out[i] + p[i] : (p[i] > out[i] ? p[i] : out[i]);
@@ -593,33 +497,32 @@ hipError_t tie_audit_read_rcas(unsigned long long out[5], bool reset)
 {
 #ifdef OVRFSR_TIE_AUDIT
     out[4] = (unsigned long long)ovrfsr_fast::kRcasTieBits; // the band the listed count belongs to: 2^-out[4] byte
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ovrfsr_tie_audit_rcas), 4 * sizeof(unsigned long long));
-    if (e == hipSuccess && reset) {
-        const unsigned long long z[4] = {0, 0, 0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ovrfsr_tie_audit_rcas), z, sizeof z);
-    }
-    return e;
+    return read_counters(HIP_SYMBOL(g_ovrfsr_tie_audit_rcas), out, 4, reset);
 #else
     (void)out; (void)reset;
     return hipErrorNotSupported;
 #endif
 }
 
+} // namespace ovrfsr
+// The forward and back passes of OVRFSR_HDR_DOMAIN_SRTM with their launchers: a file of their own inside this unit (it opens its own
+// namespaces) ...
+#include "fsr_hdr_domain.inc"
+// ... and the tile records of a gaze-capable ctx, built on the device (tile_records_kernel), likewise
+#include "fsr_tile_records.inc"
+namespace ovrfsr {
+
 hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)
 {
     launch_fresh();
-    EasuArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const EasuArgs a = prepared(a_in);
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
     const bool strict = prec == PREC_FP32_STRICT;
-    const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
+    const dim3 grid = tile_grid(a, nTiles, batch);
     const size_t lds = easu_lds_bytes(prec, in_fmt, a.cellsW, a.cellsH);
     if (in_fmt == FMT_RGBA8_MS4) { // resolve fused into the staging sweep: only where easu_msaa_fused_ok says so
-        const bool masked = a.tileList || a.m.mode[0] != MASK_ALL_INSIDE || a.m.mode[1] != MASK_ALL_INSIDE;
-        if (masked || !easu_msaa_fused_ok(prec, out_fmt, a.cellsW)) return hipErrorInvalidValue;
-        easu_fast_go<FMT_RGBA8_MS4, FMT_RGBA8, false>(easu_kernel_pitch(a.cellsW), a, grid, s);
-        return hipGetLastError();
+        if (a.tileList || is_masked(a.m) || !easu_msaa_fused_ok(prec, out_fmt, a.cellsW)) return hipErrorInvalidValue;
+        return easu_fast_go<FMT_RGBA8_MS4, FMT_RGBA8, false>(easu_kernel_pitch(a.cellsW), a, grid, s);
     }
     if (in_fmt == FMT_R11G11B10F) return strict ? hipErrorInvalidValue : launch_easu_packed(out_fmt, a, grid, s); // fsr_packed_kernels.hip
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, easu_go, strict, a, grid, lds, s)
@@ -628,14 +531,12 @@ hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, 
 hipError_t launch_rcas(int prec, int in_fmt, int out_fmt, const RcasArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)
 {
     launch_fresh();
-    RcasArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
-    a.dppTilesXMagic = div_magic((uint32_t)(a.v.outW + kRcasDppTileW - 1) / kRcasDppTileW);
+    RcasArgs a = prepared(a_in);
+    a.dppTilesXMagic = div_magic(rcas_dpp_tiles_x(a.v.outW));
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT && prec != PREC_FP32_EXACT) return hipErrorInvalidValue;
     const bool strict = prec == PREC_FP32_STRICT, exact = prec == PREC_FP32_EXACT;
     if (a.tileList && (strict || nTiles == 0)) return hipErrorInvalidValue; // lists are a product-build feature
-    const dim3 grid(a.tileList ? nTiles : a.tilesX * a.tilesY, 1, batch);
-    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, rcas_go, strict, exact, a, grid, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, rcas_go, strict, exact, a, tile_grid(a, nTiles, batch), s)
 }
 
 } // namespace ovrfsr

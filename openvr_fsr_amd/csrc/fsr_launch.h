@@ -1,4 +1,6 @@
-// fsr_launch.h -- typed launchers implemented in fsr_kernels.hip, used by the host launch manager.
+// fsr_launch.h -- the typed launchers the host launch manager calls: declarations only.  They are implemented in the kernel units
+// (fsr_kernels.hip, fsr_packed_kernels.hip, nis_kernels.hip), out of the pieces in fsr_launch_impl.h; every one of them clears the thread's
+// pending HIP error before it launches (launch_fresh there), so what it returns is its own launch's.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -6,12 +8,6 @@
 #include "fsr_sizes.h" // the size rules the launchers go by (and the pipeline planner decides by)
 
 namespace ovrfsr {
-// HIP keeps a host thread's last error until somebody reads it, and a kernel launch reports its failure only there.  Every launch_* below
-// reads (= clears) it BEFORE launching, so that what it returns afterwards is its own launch's -- not an error the HOST's code left behind:
-// a failed hipMalloc of the caller's, handled through its return value, used to fail the next frame as "EASU launch: out of memory"
-// (tests/debug/stale_error.c, round 6).
-inline void launch_fresh() { (void)hipGetLastError(); }
-
 hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a, uint32_t batch, hipStream_t s, uint32_t nTiles = 0);
 hipError_t launch_easu_outside(int in_fmt, int mid_fmt, int out_fmt, const EasuArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_fused(int prec, int in_fmt, int mid_fmt, int out_fmt, const FusedArgs &a, uint32_t batch, hipStream_t s, uint32_t nTiles = 0);
@@ -52,32 +48,4 @@ hipError_t tie_audit_read_rcas(unsigned long long out[5], bool reset); // the sa
 hipError_t bounds_read_fsr(unsigned long long *out, bool reset);
 hipError_t bounds_read_nis(unsigned long long *out, bool reset);
 hipError_t bounds_selftest();
-// `return FN<in_fmt, out_fmt>(args)` of a launcher's run-time `in_fmt` / `out_fmt`: the nine pairs of RGBA8 / RGBA16F / RGBA32F, then TAIL --
-// OVRFSR_TEN_BIT_PAIRS: R10G10B10A2, only what the reference's 10-bit path needs (10-bit in -> 10-bit out, PostProcessor.cpp:63-74) plus a
-// float destination for un-quantised parity checks; OVRFSR_NO_TEN_BIT: kernels that are not built for it (fused, LDS-staged outside)
-#define OVRFSR_DISPATCH_FMT(TAIL, FN, ...)                               \
-    switch (in_fmt < 3 && out_fmt < 3 ? in_fmt * 3 + out_fmt : -1) {     \
-    case 0: return FN<FMT_RGBA8, FMT_RGBA8>(__VA_ARGS__);                \
-    case 1: return FN<FMT_RGBA8, FMT_RGBA16F>(__VA_ARGS__);              \
-    case 2: return FN<FMT_RGBA8, FMT_RGBA32F>(__VA_ARGS__);              \
-    case 3: return FN<FMT_RGBA16F, FMT_RGBA8>(__VA_ARGS__);              \
-    case 4: return FN<FMT_RGBA16F, FMT_RGBA16F>(__VA_ARGS__);            \
-    case 5: return FN<FMT_RGBA16F, FMT_RGBA32F>(__VA_ARGS__);            \
-    case 6: return FN<FMT_RGBA32F, FMT_RGBA8>(__VA_ARGS__);              \
-    case 7: return FN<FMT_RGBA32F, FMT_RGBA16F>(__VA_ARGS__);            \
-    case 8: return FN<FMT_RGBA32F, FMT_RGBA32F>(__VA_ARGS__);            \
-    default: break;                                                      \
-    }                                                                    \
-    TAIL(FN, __VA_ARGS__)                                                \
-    return hipErrorInvalidValue;
-#define OVRFSR_TEN_BIT_PAIRS(FN, ...)                                                                      \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGB10A2) return FN<FMT_RGB10A2, FMT_RGB10A2>(__VA_ARGS__); \
-    if (in_fmt == FMT_RGB10A2 && out_fmt == FMT_RGBA32F) return FN<FMT_RGB10A2, FMT_RGBA32F>(__VA_ARGS__);
-#define OVRFSR_NO_TEN_BIT(FN, ...)
-// the kernel argument block as launched: checked builds add the dynamic LDS size of the launch
-#ifdef OVRFSR_BOUNDS
-template <typename A> static inline A with_lds(A a, size_t lds) { a.ldsBytes = (uint32_t)lds; return a; }
-#else
-template <typename A> static inline const A &with_lds(const A &a, size_t) { return a; }
-#endif
 } // namespace ovrfsr

@@ -30,77 +30,36 @@ namespace ovrfsr_fast {
 } // namespace ovrfsr_fast
 #pragma clang fp contract(on)
 
+// The launchers: fsr_kernels.hip's pieces (fsr_launch_impl.h) on this unit's instances.  The order in which they name the kernels is the
+// order of the kernels in this code object (see there).
+#define OVRFSR_LAUNCH_FSR 1
+#include "fsr_launch_impl.h"
+
 namespace ovrfsr {
 
-constexpr int I = FMT_R11G11B10F;
-
-template <int O, bool M>
-static void easu_packed_go(int pitch, const EasuArgs &a, dim3 grid, hipStream_t s)
-{
-    const size_t lds = (size_t)pitch * a.cellsH * 36 + (size_t)pitch * kLumPadRows * 4; // colour + analysis (float4) + luma planes + pad rows
-    if (pitch == 28) hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 28, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    else if (pitch == 32) hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 32, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    else hipLaunchKernelGGL((ovrfsr_fast::easu_fast_kernel<I, O, 40, M>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-}
-template <int O>
+template <int I, int O>
 static hipError_t easu_packed(const EasuArgs &a, dim3 grid, hipStream_t s)
 {
     const int pitch = easu_kernel_pitch(a.cellsW);
     if (pitch == 0) return hipErrorInvalidValue; // wider footprints have no instance: the launch manager sends them through the resolve pass
-    if (a.m.mode[0] != MASK_ALL_INSIDE || a.m.mode[1] != MASK_ALL_INSIDE) easu_packed_go<O, true>(pitch, a, grid, s);
-    else easu_packed_go<O, false>(pitch, a, grid, s);
-    return hipGetLastError();
+    return is_masked(a.m) ? easu_fast_go<I, O, true>(pitch, a, grid, s) : easu_fast_go<I, O, false>(pitch, a, grid, s);
 }
 
-// (the dynamic-LDS cap is raised per kernel instantiation and device: fused_go3, fsr_kernels.hip)
-template <int M, int O, int PITCH>
-static hipError_t fused_packed_go(const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
-{
-    static std::atomic<uint64_t> done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ovrfsr_fast::fused_kernel<I, M, O, PITCH, kFusedThreads>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFusedLdsMax);
-        if (e != hipSuccess) return e;
-        done.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((ovrfsr_fast::fused_kernel<I, M, O, PITCH, kFusedThreads>), grid, dim3(kFusedThreads), lds, s, with_lds(a, lds));
-    return hipGetLastError();
-}
 // the words decode to RGBA16F texels: a half or a float intermediate, as for an RGBA16F input
-template <int O>
+template <int I, int O>
 static hipError_t fused_packed(int mid_fmt, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s)
 {
-    const int pitch = easu_fast_pitch(a.cellsW);
-    if (pitch == 0) return hipErrorInvalidValue;
-    if (mid_fmt == FMT_RGBA16F) return pitch == 32 ? fused_packed_go<FMT_RGBA16F, O, 32>(a, grid, lds, s) : fused_packed_go<FMT_RGBA16F, O, 40>(a, grid, lds, s);
-    if (mid_fmt == FMT_RGBA32F) return pitch == 32 ? fused_packed_go<FMT_RGBA32F, O, 32>(a, grid, lds, s) : fused_packed_go<FMT_RGBA32F, O, 40>(a, grid, lds, s);
-    return hipErrorInvalidValue;
+    return fused_go<FusedFast, I, O, FMT_RGBA8, FMT_RGBA16F, FMT_RGBA32F>(mid_fmt, a, grid, lds, s);
 }
-
 // ... and behind them, under cfg.reference_formats, a UNORM8 one (the outside-tile kernel only)
-template <int O>
+template <int I, int O>
 static hipError_t easu_outside_packed(int mid_fmt, const EasuArgs &a, dim3 grid, hipStream_t s)
 {
-    if (mid_fmt < 0) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, -1>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == FMT_RGBA16F) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, FMT_RGBA16F>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == FMT_RGBA32F) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, FMT_RGBA32F>), grid, dim3(kThreads), 0, s, a);
-    else if (mid_fmt == FMT_RGBA8) hipLaunchKernelGGL((ovrfsr_fast::easu_outside_kernel<I, O, FMT_RGBA8>), grid, dim3(kThreads), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return easu_outside_go<I, O, -1, FMT_RGBA16F, FMT_RGBA32F, FMT_RGBA8>(mid_fmt, a, grid, s);
 }
 
 // the destination of a launch from packed words: RGBA8, RGBA16F or RGBA32F
-#define OVRFSR_PACKED_OUT(FN, ...)                                  \
-    switch (out_fmt) {                                              \
-    case FMT_RGBA8: return FN<FMT_RGBA8>(__VA_ARGS__);              \
-    case FMT_RGBA16F: return FN<FMT_RGBA16F>(__VA_ARGS__);          \
-    case FMT_RGBA32F: return FN<FMT_RGBA32F>(__VA_ARGS__);          \
-    default: return hipErrorInvalidValue;                           \
-    }
+#define OVRFSR_PACKED_OUT(FN, ...) OVRFSR_DISPATCH_OUT(FMT_R11G11B10F, FN, __VA_ARGS__) return hipErrorInvalidValue;
 
 hipError_t launch_easu_packed(int out_fmt, const EasuArgs &a, dim3 grid, hipStream_t s) { OVRFSR_PACKED_OUT(easu_packed, a, grid, s) }
 hipError_t launch_fused_packed(int mid_fmt, int out_fmt, const FusedArgs &a, dim3 grid, size_t lds, hipStream_t s) { OVRFSR_PACKED_OUT(fused_packed, mid_fmt, a, grid, lds, s) }
@@ -109,13 +68,7 @@ hipError_t launch_easu_outside_packed(int mid_fmt, int out_fmt, const EasuArgs &
 hipError_t tie_audit_read_packed(unsigned long long out[6], bool reset)
 {
 #ifdef OVRFSR_TIE_AUDIT
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ovrfsr_tie_audit), 6 * sizeof(unsigned long long));
-    if (e == hipSuccess && reset) {
-        const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ovrfsr_tie_audit), z, sizeof z);
-    }
-    return e;
+    return read_counters(HIP_SYMBOL(g_ovrfsr_tie_audit), out, 6, reset);
 #else
     for (int i = 0; i < 6; ++i) out[i] = 0;
     (void)reset;

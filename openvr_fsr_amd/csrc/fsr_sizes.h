@@ -1,5 +1,5 @@
 // fsr_sizes.h -- the size rules of the kernels: LDS pitches, LDS bytes, and which kernel a shape may take.  Host only, inline, no HIP call:
-// the pipeline planner (pipeline_plan.cpp) decides by them and the launchers (fsr_kernels.hip, nis_kernels.hip) launch by them, so that
+// the pipeline planner (pipeline_plan.cpp) decides by them and the launchers (fsr_kernels.hip, fsr_packed_kernels.hip, nis_kernels.hip) launch by them, so that
 // what the planner accepts is what the launchers can run.
 #pragma once
 #include <stddef.h>
@@ -55,6 +55,20 @@ inline bool outside_staged_ok(const BatchView &v, int in_fmt) { return v.inW <= 
 inline bool easu_msaa_fused_ok(int prec, int out_fmt, int cellsW)
 {
     return prec == PREC_FP32 && out_fmt == FMT_RGBA8 && easu_kernel_pitch(cellsW) != 0;
+}
+
+// rcas_dpp_kernel's grid for an unmasked launch: tiles of 62 stored columns by `rows` (kRcasDppTileH = 32, or 16) rows
+inline uint32_t rcas_dpp_tiles_x(int outW) { return (uint32_t)(outW + kRcasDppTileW - 1) / kRcasDppTileW; }
+inline uint32_t rcas_dpp_tiles_y(int outH, int rows) { return (uint32_t)(outH + rows - 1) / rows; }
+// ... and its height for such a launch of `batch` images: true = the 16-row form.  Small launches: the grid is r = workgroups /
+// kRcasResident rounds of the resident workgroups, the last one partly filled; half-height workgroups run ceil(2r) rounds of half the
+// length (3 % more work per pixel).  One C2 eye image: r = 1.41, 2 rounds against 3 half rounds = 1.5 (14.4 instead of 15.5 us,
+// profiles/r05_frame.txt); a batch: no difference, the 8-row form wins
+inline bool rcas_dpp_small(int outW, int outH, uint32_t batch)
+{
+    const uint64_t wgs = (uint64_t)rcas_dpp_tiles_x(outW) * rcas_dpp_tiles_y(outH, kRcasDppTileH) * batch;
+    const uint64_t full = (wgs + kRcasResident - 1) / kRcasResident, half = (2 * wgs + kRcasResident - 1) / kRcasResident;
+    return wgs < 16 * kRcasResident && 103 * half < 200 * full;
 }
 
 // rows of the resolve pass's destination: texels of the format the pipeline sees (R11G11B10F: 4-byte words in, RGBA16F out), padded to 16 bytes

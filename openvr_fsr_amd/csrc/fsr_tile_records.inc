@@ -35,10 +35,9 @@ hipError_t launch_tile_records(const TileRecordsArgs &a, hipStream_t s)
     if (n == 0) return hipSuccess; // (both regions empty: nothing to build)
     if (n > a.regionEntries || a.g.tileW != (uint32_t)kTileW) return hipErrorInvalidValue;
     const dim3 grid((n + 255u) / 256u, 2, 1);
-    if (a.g.tileH == 32u) hipLaunchKernelGGL((ovrfsr_fast::tile_records_kernel<32>), grid, dim3(256), 0, s, a);
-    else if (a.g.tileH == 24u) hipLaunchKernelGGL((ovrfsr_fast::tile_records_kernel<24>), grid, dim3(256), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (a.g.tileH == 32u) return launch_kernel<ovrfsr_fast::tile_records_kernel<32>>(grid, dim3(256), 0, s, a);
+    if (a.g.tileH == 24u) return launch_kernel<ovrfsr_fast::tile_records_kernel<24>>(grid, dim3(256), 0, s, a);
+    return hipErrorInvalidValue;
 }
 
 } // namespace ovrfsr

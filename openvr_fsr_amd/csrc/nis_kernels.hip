@@ -21,6 +21,8 @@ namespace ovrfsr_strict {
 } // namespace ovrfsr_strict
 #pragma clang fp contract(on)
 
+#include "fsr_launch_impl.h"
+
 namespace ovrfsr {
 
 template <int I, int O>
@@ -28,43 +30,35 @@ static hipError_t scaler_go(bool strict, const NisArgs &a, dim3 grid, size_t lds
 {
     const int pitch = nis_pitch(a.cellsW);
     if (pitch == 32) {
-        if (strict) hipLaunchKernelGGL((ovrfsr_strict::nis_scaler_kernel<I, O, 32>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-        else hipLaunchKernelGGL((ovrfsr_fast::nis_scaler_kernel<I, O, 32>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    } else if (pitch == 40) {
-        if (strict) hipLaunchKernelGGL((ovrfsr_strict::nis_scaler_kernel<I, O, 40>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-        else hipLaunchKernelGGL((ovrfsr_fast::nis_scaler_kernel<I, O, 40>), grid, dim3(kThreads), lds, s, with_lds(a, lds));
-    } else {
-        return hipErrorInvalidValue;
+        if (strict) return launch_kernel<ovrfsr_strict::nis_scaler_kernel<I, O, 32>>(grid, dim3(kThreads), lds, s, a);
+        return launch_kernel<ovrfsr_fast::nis_scaler_kernel<I, O, 32>>(grid, dim3(kThreads), lds, s, a);
     }
-    return hipGetLastError();
+    if (pitch == 40) {
+        if (strict) return launch_kernel<ovrfsr_strict::nis_scaler_kernel<I, O, 40>>(grid, dim3(kThreads), lds, s, a);
+        return launch_kernel<ovrfsr_fast::nis_scaler_kernel<I, O, 40>>(grid, dim3(kThreads), lds, s, a);
+    }
+    return hipErrorInvalidValue;
 }
 template <int I, int O>
 static hipError_t sharpen_go(bool strict, const NisArgs &a, dim3 grid, hipStream_t s)
 {
-    if (strict) hipLaunchKernelGGL((ovrfsr_strict::nis_sharpen_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
-    else hipLaunchKernelGGL((ovrfsr_fast::nis_sharpen_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
-    return hipGetLastError();
+    if (strict) return launch_kernel<ovrfsr_strict::nis_sharpen_kernel<I, O>>(grid, dim3(kThreads), 0, s, a);
+    return launch_kernel<ovrfsr_fast::nis_sharpen_kernel<I, O>>(grid, dim3(kThreads), 0, s, a);
 }
 
 template <int I, int O>
 static hipError_t nis_outside_go(const NisArgs &a, dim3 grid, hipStream_t s)
 {
-    hipLaunchKernelGGL((ovrfsr_fast::nis_outside_kernel<I, O>), grid, dim3(kThreads), 0, s, a);
-    return hipGetLastError();
+    return launch_kernel<ovrfsr_fast::nis_outside_kernel<I, O>>(grid, dim3(kThreads), 0, s, a);
 }
 
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a_in, uint32_t nGroups, uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    NisArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const NisArgs a = prepared(a_in);
     if (!a.tileList || nGroups == 0) return hipErrorInvalidValue;
-    if (a.bilX && a.bilY && a.tileRec && outside_staged_ok(a.v, in_fmt)) { // no records: the per-pixel kernel below needs none
-        OutsideArgs o;
-        o.v = a.v; o.tilesX = a.tilesX; o.tileList = a.tileList; o.tileRec = a.tileRec; o.bilX = a.bilX; o.bilY = a.bilY; o.debug = a.reserved1 != 0.0f ? 1u : 0u;
-        o.lds_cols = a.outsideCols; o.lds_rows = a.outsideRows;
-        return launch_outside_staged(24, in_fmt, FMT_RGBA32F, out_fmt, o, nGroups, batch, s);
-    }
+    if (a.bilX && a.bilY && a.tileRec && outside_staged_ok(a.v, in_fmt)) // no records: the per-pixel kernel below needs none
+        return launch_outside_staged(24, in_fmt, FMT_RGBA32F, out_fmt, outside_args(a, a.reserved1 != 0.0f ? 1u : 0u), nGroups, batch, s);
     const dim3 grid(nGroups, 1, batch);
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, nis_outside_go, a, grid, s)
 }
@@ -72,12 +66,10 @@ hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a_in, uint
 hipError_t launch_nis_scaler(int prec, int in_fmt, int out_fmt, const NisArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nGroups)
 {
     launch_fresh();
-    NisArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const NisArgs a = prepared(a_in);
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
-    const dim3 grid(a.tileList ? nGroups : a.tilesX * a.tilesY, 1, batch);
     const size_t lds = nis_scaler_lds_bytes(a.cellsW, a.cellsH);
-    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, scaler_go, prec == PREC_FP32_STRICT, a, grid, lds, s)
+    OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, scaler_go, prec == PREC_FP32_STRICT, a, tile_grid(a, nGroups, batch), lds, s)
 }
 
 #ifdef OVRFSR_BOUNDS
@@ -89,8 +81,7 @@ hipError_t bounds_read_nis(unsigned long long *, bool) { return hipErrorNotSuppo
 hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &a_in, uint32_t batch, hipStream_t s)
 {
     launch_fresh();
-    NisArgs a = a_in;
-    a.tilesXMagic = div_magic(a.tilesX);
+    const NisArgs a = prepared(a_in);
     if (prec != PREC_FP32 && prec != PREC_FP32_STRICT) return hipErrorInvalidValue;
     const dim3 grid(a.tilesX * a.tilesY, 1, batch);
     OVRFSR_DISPATCH_FMT(OVRFSR_TEN_BIT_PAIRS, sharpen_go, prec == PREC_FP32_STRICT, a, grid, s)

@@ -70,7 +70,7 @@ def _rcas_oracle(img8, sharp=rcas_ties.SHARP):
 
 
 def dpp_rows(ow, oh, n):
-    """rows per workgroup of the unmasked DPP form for a launch of n images: the arithmetic of rcas_dpp_small (fsr_kernels.hip)"""
+    """rows per workgroup of the unmasked DPP form for a launch of n images: the arithmetic of rcas_dpp_small (fsr_sizes.h)"""
     wgs = ((ow + 61) // 62) * ((oh + 31) // 32) * n
     full, half = (wgs + 2047) // 2048, (2 * wgs + 2047) // 2048
     return 16 if wgs < 16 * 2048 and 103 * half < 200 * full else 32

@@ -81,7 +81,7 @@ def test_thread_sanitizer_build_is_live(gpu):
 def test_a_pending_hip_error_of_the_callers_does_not_fail_the_next_apply(gpu):
     """HIP keeps a thread's last error until it is read, and a launch reports failure only there: the host's own failed hipMalloc (handled
     through its return value) used to fail the next frame as "EASU launch: out of memory".  Every launch_* now clears the state first
-    (csrc/fsr_launch.h launch_fresh); tests/debug/stale_error.c: apply, provoke the error, apply and reset + rebuild -- same pixels."""
+    (csrc/fsr_launch_impl.h launch_fresh); tests/debug/stale_error.c: apply, provoke the error, apply and reset + rebuild -- same pixels."""
     r = subprocess.run([_c_driver("stale_error")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "neither failed nor changed" in r.stdout, (r.stdout + r.stderr)[-2000:]
 

@@ -190,7 +190,7 @@ def counters_rcas(reset=False):
 
 
 def dpp_rows(ow, oh, n):
-    """rows per workgroup rcas_dpp_kernel takes for an unmasked launch of n images (fsr_kernels.hip, rcas_dpp_small)"""
+    """rows per workgroup rcas_dpp_kernel takes for an unmasked launch of n images (fsr_sizes.h, rcas_dpp_small)"""
     wgs = ((ow + 61) // 62) * ((oh + 31) // 32) * n
     full, half = (wgs + 2047) // 2048, (2 * wgs + 2047) // 2048
     return 16 if wgs < 16 * 2048 and 103 * half < 200 * full else 32
