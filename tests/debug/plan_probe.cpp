@@ -4,7 +4,8 @@
 //   plan_probe --refusals        one line per refusal the planner can produce: <status>\t<text>
 //   plan_probe CASES             one JSON line per line of the file CASES:
 //       the 25 fields tests/debug/plan_serial.h names (plan_serial::Case)
-//   Each line reports the refusal or the plan (form, formats, stage selection, list sizes), the destination refusal and resolve_in_staging
+//   Each line reports the refusal or the plan (form, formats, stage selection, list sizes, the EASU and fused-kernel LDS footprints "cells" /
+//   "fused_cells" and the bilinear footprint bound "outside_cols" / "outside_rows" of the outside-tile kernel), the destination refusal and resolve_in_staging
 //   for the destination, "unorm8_guard" (is the guard of an EASU launch from the pipeline format into RGBA8 switched on: easu_tie_half_min),
 //   "invariants": "ok" or the first structural invariant of the plan's tables that does not hold, and "digest": the FNV-1a digest of the
 //   whole plan serialised by value (plan_serial.h).
@@ -148,11 +149,13 @@ int main(int argc, char **argv)
             const Refusal dr = destination_refusal(p, d);
             std::printf(", \"form\": %s, \"out\": [%u, %u], \"upscale\": %d, \"sharpen\": %d, \"pipeline\": %u, \"mid\": %u, \"owned\": %u, \"tile_lists\": %d, "
                         "\"overlap\": %d, \"lists_shared\": %d, \"dest_status\": %d, \"dest_text\": %s, \"dest_disables\": %d, \"resolve_in_staging\": %d, "
-                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"unorm8_guard\": %d, \"invariants\": %s, \"digest\": \"%s\"",
+                        "\"inside\": [%u, %u], \"ring\": [%u, %u], \"outside\": [%u, %u], \"spans\": [%u, %u], \"unorm8_guard\": %d, \"cells\": [%d, %d], \"fused_cells\": [%d, %d], "
+                        "\"outside_cols\": %u, \"outside_rows\": [%u, %u], \"invariants\": %s, \"digest\": \"%s\"",
                         quoted(form_name(p.form)).c_str(), p.outputWidth, p.outputHeight, (int)p.doUpscale, (int)p.doSharpen, p.pipelineFormat,
                         p.intermediateFormat, p.ownedFormat, (int)p.tileLists, (int)p.overlapOutside, (int)p.listsShared, dr.status, quoted(dr.text).c_str(),
                         (int)dr.disables, (int)resolve_in_staging(p, d), p.nInside[0], p.nInside[1], p.nRing[0], p.nRing[1], p.nOutside[0], p.nOutside[1],
                         p.nSpans[0], p.nSpans[1], (int)std::isfinite(easu_tie_half_min(p, p.pipelineFormat, OVRFSR_FORMAT_RGBA8_UNORM, INFINITY)),
+                        p.cellsW, p.cellsH, p.fusedCellsW, p.fusedCellsH, p.outsideCols, p.outsideRows[0], p.outsideRows[1],
                         quoted(invariants(p).c_str()).c_str(), plan_serial::digest(p).c_str());
         }
         std::printf("}\n");
