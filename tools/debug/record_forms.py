@@ -9,6 +9,10 @@ planner's predictions (status, text, owned format) against it without a GPU.
 
     python tools/debug/record_forms.py OUT.json        (GPU)
 
+run_case(case, content=..., arrays=True) also hands back the output arrays it hashed, and runs the case on uniform-random content where asked:
+tests/test_gpu_launch_forms_oracle.py compares those arrays with the CPU oracle (tests/forms_model.py, which reads the eye images from
+source_array(), the numpy half of the upload).  The record itself is always taken on the structured content and holds no arrays.
+
 The matrix (cases()):
   * RGBA8 source, ctx-owned output: the full factorial of precision {0, 2, 3} x use_nis x stage_mask {0, 1, 2} x fused {-1, 0, 1} x
     quantize_intermediate x reference_formats x mask {off, on};
@@ -140,39 +144,48 @@ def cases():
 _SRC_CACHE = {}
 
 
-def _source(src, w, h, seed):
-    """the device tensor of an eye image (tests/synth.structured_u8 in the source's format) and its ovrfsr_format override"""
+CONTENTS = ("structured", "random")   # tests/synth.structured_u8 (what the record was taken on), tests/synth.random_u8
+
+
+def source_array(src, w, h, seed, content="structured"):
+    """the numpy half of _source: the array that is uploaded (the content generator's uint8 image in the source's format) and its
+    ovrfsr_format override.  tests/forms_model.decoded() reads the image the pipeline sees from this same array."""
     import numpy as np
-    import torch
     from tests import synth
-    key = (src, w, h, seed)
-    if key in _SRC_CACHE:
-        return _SRC_CACHE[key]
-    dev = torch.device("cuda")
-    u8 = synth.structured_u8(w, h, seed)
+    gen = {"structured": synth.structured_u8, "random": synth.random_u8}[content]
+    u8 = gen(w, h, seed)
     fmt = None
     if src == "rgba8":
-        t = torch.from_numpy(u8).to(dev)
+        a = u8
     elif src == "bgra8":
-        t, fmt = torch.from_numpy(np.ascontiguousarray(u8[..., [2, 1, 0, 3]])).to(dev), BGRA8
+        a, fmt = np.ascontiguousarray(u8[..., [2, 1, 0, 3]]), BGRA8
     elif src in ("rgba16f", "rgba32f"):
         f = u8.astype(np.float32) / np.float32(255)
-        t = torch.from_numpy(f.astype(np.float16) if src == "rgba16f" else f).to(dev)
+        a = f.astype(np.float16) if src == "rgba16f" else f
     elif src == "rgb10a2":
         v = u8.astype(np.uint32) * 4 + (u8.astype(np.uint32) >> 6)
-        t = torch.from_numpy((v[..., 0] | v[..., 1] << 10 | v[..., 2] << 20 | np.uint32(3) << 30).view(np.int32)).to(dev)
+        a = (v[..., 0] | v[..., 1] << 10 | v[..., 2] << 20 | np.uint32(3) << 30).view(np.int32)
     elif src == "r11g11b10f":
         v = u8.astype(np.uint32)  # finite words only: exponent fields stay below 31
-        t, fmt = torch.from_numpy((v[..., 0] * 4 | (v[..., 1] * 4) << 11 | (v[..., 2] * 2) << 22).view(np.int32)).to(dev), R11G11B10F
+        a, fmt = (v[..., 0] * 4 | (v[..., 1] * 4) << 11 | (v[..., 2] * 2) << 22).view(np.int32), R11G11B10F
     elif src == "ms4_rgba8":
-        t = torch.from_numpy(np.stack([synth.structured_u8(w, h, seed + 10 * s) for s in range(4)], axis=2)).to(dev)
+        a = np.stack([gen(w, h, seed + 10 * s) for s in range(4)], axis=2)
     elif src == "ms2_rgba16f":
-        t = torch.from_numpy(np.stack([(synth.structured_u8(w, h, seed + 10 * s).astype(np.float32) / np.float32(255)).astype(np.float16)
-                                       for s in range(2)], axis=2)).to(dev)
+        a = np.stack([(gen(w, h, seed + 10 * s).astype(np.float32) / np.float32(255)).astype(np.float16) for s in range(2)], axis=2)
     else:
         raise ValueError(src)
-    _SRC_CACHE[key] = (t, fmt)
-    return t, fmt
+    return a, fmt
+
+
+def _source(src, w, h, seed, content="structured"):
+    """the device tensor of an eye image (source_array, uploaded) and its ovrfsr_format override"""
+    import torch
+    key = (src, w, h, seed, content)
+    if key in _SRC_CACHE:
+        return _SRC_CACHE[key]
+    a, fmt = source_array(src, w, h, seed, content)
+    _SRC_CACHE[key] = (torch.from_numpy(a).to(torch.device("cuda")), fmt)
+    return _SRC_CACHE[key]
 
 
 def _dest(dst, ow, oh, n=None):
@@ -185,17 +198,24 @@ def _dest(dst, ow, oh, n=None):
     return torch.zeros(lead + (oh, ow, 4), dtype=dt, device=dev), (BGRA8 if dst == "bgra8" else None)
 
 
-def _sha(*tensors):
-    import torch
-    torch.cuda.synchronize()
+def sha_of(arrays):
+    """the SHA-256 the record holds, of the output arrays in the order run_case hands them back"""
     h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.contiguous().cpu().numpy().tobytes())
+    for a in arrays:
+        h.update(a.tobytes())
     return h.hexdigest()
 
 
-def run_case(case):
-    """-> {"calls": [[status, text], ...], "owned_format": format or None, "sha256": hex or None}; "create": status where ovrfsr_create refused"""
+def _host(*tensors):
+    import torch
+    torch.cuda.synchronize()
+    return [t.contiguous().cpu().numpy() for t in tensors]
+
+
+def run_case(case, content="structured", arrays=False):
+    """-> {"calls": [[status, text], ...], "owned_format": format or None, "sha256": hex or None}; "create": status where ovrfsr_create refused.
+    content: the generator of the eye images (CONTENTS; the record is taken on "structured").  arrays = True adds "arrays": the outputs
+    that were hashed, as numpy arrays in the order they were hashed (None where nothing was)."""
     import torch
     import openvr_fsr_amd as A
     from openvr_fsr_amd.postprocessor import _wrap, image_of
@@ -213,12 +233,20 @@ def run_case(case):
         return rc
 
     rec = dict(calls=calls, owned_format=None, sha256=None)
+    if arrays:
+        rec["arrays"] = None
+
+    def done(*tensors):
+        host = _host(*tensors)
+        rec["sha256"] = sha_of(host)
+        if arrays:
+            rec["arrays"] = host
     kind, src, dst = case["kind"], case["src"], case["dst"]
     try:
         if kind in ("batch4", "shared"):
             n = 4 if kind == "batch4" else 2
-            t0, fmt = _source(src, iw, ih, 3)
-            t1, _ = _source(src, iw, ih, 4)
+            t0, fmt = _source(src, iw, ih, 3, content)
+            t1, _ = _source(src, iw, ih, 4, content)
             texs = torch.stack([t0, t1] * (n // 2))
             outs, ofmt = _dest(dst, ow, oh, n)
             i0, o0 = image_of(texs[0], fmt), image_of(outs[0], ofmt)
@@ -226,7 +254,7 @@ def run_case(case):
             for _ in range(2):
                 rc = call(L.ovrfsr_apply_batch(pp._ctx, n, 0, 1, *args) if kind == "batch4" else L.ovrfsr_apply_batch_shared(pp._ctx, n, *args))
                 if rc == 0:
-                    rec["sha256"] = _sha(outs)
+                    done(outs)
                     break
             return rec
         eyes = (0, 1) if kind == "pair" else (0,)
@@ -235,7 +263,7 @@ def run_case(case):
             pp.set_config(cfg)
         results = []
         for eye in eyes:
-            tex, fmt = _source(src, iw, ih, 3 + eye)
+            tex, fmt = _source(src, iw, ih, 3 + eye, content)
             img = image_of(tex, fmt)
             out, ofmt = (None, None) if dst == "owned" else _dest(dst, ow, oh)
             oimg = image_of(out, ofmt) if out is not None else A.Image()
@@ -249,7 +277,7 @@ def run_case(case):
                 rec["owned_format"] = int(oimg.format)
                 out = tex if oimg.data == tex.data_ptr() else _wrap(oimg, tex.device)
             results.append(out)
-        rec["sha256"] = _sha(*results)
+        done(*results)
         return rec
     finally:
         torch.cuda.synchronize()
