@@ -506,6 +506,49 @@ OVRFSR_API int ovrfsr_get_gaze(const ovrfsr_ctx *ctx, int eye, float xy[2], int 
 /* re-aims in place and rebuilds that applies performed because of a gaze, since the ctx was created */
 OVRFSR_API int ovrfsr_gaze_stats(const ovrfsr_ctx *ctx, uint32_t *reaims, uint32_t *rebuilds);
 
+/* ---- dynamic resolution: the input size follows the renderer's viewport, per frame -----------------------
+ * An engine with dynamic resolution keeps its eye texture at a fixed allocation and renders into a viewport whose size changes from frame to
+ * frame; the compositor's target does not move.  Without these calls an input-size change is a full reset: every table and ctx-owned image
+ * freed (the output the compositor may still hold included), everything re-planned and uploaded again with blocking copies, the device
+ * synchronised by the frees.  With a MAXIMUM input size declared, an apply whose input size differs from the planned one RE-SCALES IN PLACE
+ * as long as format, eye layout and output size stay the same.  No ABI version and no config field changes with these: a host probes for
+ * the symbols.
+ *
+ * max_width, max_height: 1..16384 texels per axis, the allocation's size; (0, 0) clears the setting.  Like ovrfsr_set_hidden_area and
+ * ovrfsr_set_hdr_domain the setter drops a recorded pair_submit eye, enables a disabled ctx again and makes the next apply plan afresh; it
+ * touches no device resource itself, so it is accepted under stream capture.  ovrfsr_reset and ovrfsr_set_config keep the value.
+ *
+ * THE RULE.  With a maximum set, every call behaves as the same call on a fresh ctx -- same cfg, meshes, gazes and HDR domain, the same
+ * maximum set -- that never saw another input size: status, error text, the image handed back, every byte written,
+ * ovrfsr_hidden_area_stats; in every form, format, build and precision, for batches, shared side-by-side textures and pair_submit (a texture
+ * of another size is still "a recorded eye whose other eye does not follow": the recorded eye is launched first, at its own size).  Only
+ * the cost differs, and the address of the ctx-owned output does not move across re-scales.
+ *
+ * WHAT AN APPLY AFTER AN INPUT-SIZE CHANGE DOES, one of three (ovrfsr_rescale_stats counts the first and the second):
+ *   - a RE-SCALE in place: the new size is within the maximum and the plan of the new size differs from the current one in nothing but the
+ *     input size, the EASU / NIS constants, the LDS footprints, the bilinear tap tables and the tile records.  No allocation, no blocking
+ *     copy, no host wait, nothing freed: the tap tables are refilled and the records rebuilt on the device, on the call's stream; the
+ *     launches behind them read the new constants.  Every buffer sized by the input (the multisample resolve's and the R11G11B10F unpack
+ *     pass's copy, the BGRA8 re-order's, the HDR domain's mapped copy) was allocated for the maximum when the ctx was built;
+ *   - a REBUILD, today's path: the output size moves (cfg.out_width or cfg.out_height is 0), the input now equals the output (no upscale
+ *     stage), the form, the tile lists or the outside-tile kernel's stream would change, or the size exceeds the maximum.  Where the plan
+ *     of the new size is a refusal (LDS footprint, NVScaler outside 1x..2x) the call fails exactly as on a fresh ctx and the ctx is
+ *     disabled until reset;
+ *   - nothing: the size is the planned one.
+ * A gaze that moved in the same apply is re-aimed behind the re-scale.  Under stream capture an apply that would re-scale or rebuild is
+ * refused like any build (OVRFSR_ERR_INVALID_ARGUMENT, nothing touched, the capture stays valid); a captured graph replays the size it was
+ * captured with.  Tap clamping happens at the edge of the image the call names: with `data` at the viewport's origin, `width` / `height`
+ * the viewport's and `pitch_bytes` the allocation's, no texel of the allocation outside the viewport is ever read.  A ctx on which no
+ * maximum was ever set plans, allocates, uploads and launches exactly what it always has.
+ *
+ * OVRFSR_ERR_INVALID_ARGUMENT -- the stored value left as it was -- for a NULL ctx, one axis zero and the other not, or an axis above 16384. */
+OVRFSR_API int ovrfsr_set_max_input_size(ovrfsr_ctx *ctx, uint32_t max_width, uint32_t max_height);
+/* the stored maximum, (0, 0) where none is set.  OVRFSR_ERR_INVALID_ARGUMENT for a NULL argument. */
+OVRFSR_API int ovrfsr_get_max_input_size(const ovrfsr_ctx *ctx, uint32_t *max_width, uint32_t *max_height);
+/* since the ctx was created: the applies that re-scaled in place, and the applies that rebuilt because of an input-size change while a
+ * maximum was set */
+OVRFSR_API int ovrfsr_rescale_stats(const ovrfsr_ctx *ctx, uint32_t *rescales, uint32_t *rebuilds);
+
 /* ---- constants-only entry points (known-answer tests; no GPU needed) ------------------------- */
 
 /* FsrEasuCon (src/fsr/ffx_fsr1.h:156-202); con = con0|con1|con2|con3 */

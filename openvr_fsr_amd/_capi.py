@@ -130,6 +130,10 @@ def library():
         L.ovrfsr_clear_gaze.argtypes = [C.c_void_p, C.c_int]
         L.ovrfsr_get_gaze.argtypes = [C.c_void_p, C.c_int, f32p, C.POINTER(C.c_int)]
         L.ovrfsr_gaze_stats.argtypes = [C.c_void_p, u32p, u32p]
+    if hasattr(L, "ovrfsr_set_max_input_size"):  # (probed the same way)
+        L.ovrfsr_set_max_input_size.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.ovrfsr_get_max_input_size.argtypes = [C.c_void_p, u32p, u32p]
+        L.ovrfsr_rescale_stats.argtypes = [C.c_void_p, u32p, u32p]
     if L.ovrfsr_abi_version() != 5:
         raise OvrFsrError(1, "ABI version mismatch")
     _LIB = L

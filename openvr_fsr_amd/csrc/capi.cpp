@@ -89,6 +89,14 @@ OVRFSR_API int ovrfsr_debug_bounds(unsigned long long *counts, int n, int reset)
 OVRFSR_API int ovrfsr_debug_bounds_selftest(void) { return ovrfsr::bounds_selftest() == hipSuccess ? OVRFSR_OK : OVRFSR_ERR_HIP; }
 // fault injection (checked builds only): the nth device allocation / stream / event creation of the launch manager from now on fails, once; 0 disarms
 OVRFSR_API void ovrfsr_debug_fail_resource(int nth) { ovrfsr::debug_fail_resource(nth); }
+// dynamic resolution (checked builds only): the route a re-scale refills the tap tables by from now on -- 1: host-built taps through a staging
+// slot, 0: tap_tables_kernel --, and the device tap tables read back (bytes: 8 x (outW rounded up to 32 + outH + 64))
+OVRFSR_API void ovrfsr_debug_tap_route(int upload) { ovrfsr::debug_tap_route(upload); }
+OVRFSR_API int ovrfsr_debug_read_taps(ovrfsr_ctx *ctx, void *dst, size_t bytes)
+{
+    if (!ctx || !dst) return OVRFSR_ERR_INVALID_ARGUMENT;
+    return guarded([&] { return ctx->pp->DebugReadTaps(dst, bytes); });
+}
 #endif
 
 OVRFSR_API int ovrfsr_pair_pending(const ovrfsr_ctx *ctx) { return ctx && ctx->pp && ctx->pp->PairPending() ? 1 : 0; }
@@ -176,6 +184,27 @@ OVRFSR_API int ovrfsr_gaze_stats(const ovrfsr_ctx *ctx, uint32_t *reaims, uint32
 {
     if (!ctx || !reaims || !rebuilds) return OVRFSR_ERR_INVALID_ARGUMENT;
     ctx->pp->GazeStats(reaims, rebuilds);
+    return OVRFSR_OK;
+}
+
+// ---- dynamic resolution (header).  The argument checks live here; the setter stores, the next apply plans afresh (PostProcessor::SetMaxInputSize).
+OVRFSR_API int ovrfsr_set_max_input_size(ovrfsr_ctx *ctx, uint32_t max_width, uint32_t max_height)
+{
+    if (!ctx || (max_width == 0) != (max_height == 0) || max_width > 16384 || max_height > 16384) return OVRFSR_ERR_INVALID_ARGUMENT; // the stored value stays
+    return guarded([&] { return ctx->pp->SetMaxInputSize(max_width, max_height); });
+}
+
+OVRFSR_API int ovrfsr_get_max_input_size(const ovrfsr_ctx *ctx, uint32_t *max_width, uint32_t *max_height)
+{
+    if (!ctx || !max_width || !max_height) return OVRFSR_ERR_INVALID_ARGUMENT;
+    ctx->pp->MaxInputSize(max_width, max_height);
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_rescale_stats(const ovrfsr_ctx *ctx, uint32_t *rescales, uint32_t *rebuilds)
+{
+    if (!ctx || !rescales || !rebuilds) return OVRFSR_ERR_INVALID_ARGUMENT;
+    ctx->pp->RescaleStats(rescales, rebuilds);
     return OVRFSR_OK;
 }
 

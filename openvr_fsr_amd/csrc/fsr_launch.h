@@ -37,6 +37,8 @@ hipError_t launch_hdr_forward(int fmt, const uint8_t *src, uint32_t srcPitch, ui
 hipError_t launch_hdr_back(int fmt, const uint8_t *src, uint8_t *dst, uint32_t dstPitch, uint64_t dstStride, uint32_t w, uint32_t h, uint32_t batch, hipStream_t s);
 // the 16-byte records of the first a.n[eye] entries of both list regions (fsr_tile_records.inc); no launch where both are empty
 hipError_t launch_tile_records(const TileRecordsArgs &a, hipStream_t s);
+// the column taps, their padding copies and the row taps for the two sizes of `a`, in place (fsr_tap_tables.inc)
+hipError_t launch_tap_tables(const TapTablesArgs &a, hipStream_t s);
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a, uint32_t nGroups, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s);

@@ -121,6 +121,14 @@ struct TileRecordsArgs {
     uint32_t n[2];
 };
 
+// tap_tables_kernel (fsr_tap_tables.inc): the tap tables of a rescale-capable ctx refilled in place for another input size -- entries
+// [0, tapYOff + outH) of `taps` (bilin_taps.h, tap_table_entry); the 64 spare entries behind them stay zero.
+struct TapTablesArgs {
+    BilinTap *taps;
+    uint32_t outW, outH, inW, inH;
+    uint32_t tapYOff;
+};
+
 struct RcasArgs {
     BatchView v;
     float sharp;            // FsrRcasCon con[0] as float

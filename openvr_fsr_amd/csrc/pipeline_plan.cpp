@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <utility>
+#include "bilin_taps.h"
 #include "fsr_formats.h"
 #include "fsr_sizes.h"
 
@@ -145,15 +146,7 @@ void tap_tables(Plan &p)
     p.tapYOff = (ow + (uint32_t)kTileW - 1u) & ~((uint32_t)kTileW - 1u);
     taps.assign((size_t)p.tapYOff + oh + 64, BilinTap{0, 0.0f});
     auto fill = [](BilinTap *t, uint32_t outN, uint32_t inN) {
-        for (uint32_t o = 0; o < outN; ++o) {
-            volatile float u = (float)o / (float)outN;
-            const float tt = mad2(u, (float)inN, -0.5f);
-            const float s = std::floor(mad2(tt, 256.0f, 0.5f));
-            volatile float q = s * (1.0f / 256.0f);
-            const float f = std::floor(q);
-            t[o].i0 = (int32_t)f;
-            t[o].frac = mad2(f, -256.0f, s) * (1.0f / 256.0f);
-        }
+        for (uint32_t o = 0; o < outN; ++o) t[o] = bilin_tap(o, outN, inN); // (bilin_taps.h: the rule tap_tables_kernel evaluates too)
     };
     fill(taps.data(), ow, p.inputWidth);
     for (uint32_t o = ow; o < p.tapYOff; ++o) taps[o] = taps[ow - 1];
@@ -556,8 +549,11 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
 }
 
 // the plan of one submission as it is filtered: what plan_pipeline has always been
+// `maps`: non-null lays the plan out in per-eye regions (a gaze-capable or rescale-capable plan) and leaves the hidden-area maps there.
+// `reuse`: the re-scale step (rescale_pipeline) -- the plan of another input size with the same output side: the mask constants and modes,
+// the reciprocals, the layout and everything of the lists are taken from it instead of being computed, and no table but the taps is built.
 static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                             const HiddenArea *hidden, HiddenMaps *gaze)
+                             const HiddenArea *hidden, HiddenMaps *maps, bool rescaleCapable = false, const PlanFields *reuse = nullptr)
 {
     Plan p;
     p.inputWidth = width; p.inputHeight = height; p.inputFormat = format;
@@ -598,10 +594,15 @@ static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t
         if (p.doSharpen && (p.doUpscale ? mid : pf) != OVRFSR_FORMAT_RGBA8_UNORM) return kRefusals[R_EXACT_SOURCE];
     }
 
-    for (int eye = 0; eye < 2; ++eye) {
+    for (int eye = 0; eye < 2 && !reuse; ++eye) {
         mask_constants(p.centre[eye], p.radius, ow, oh, cfg.proj_centre, cfg.radius, onlyOneEye ? 1 : 0, eye);
         const uint32_t gw = p.maskGroupW = cfg.use_nis ? 32u : 16u, gh = p.maskGroupH = cfg.use_nis ? (scaleNotOne ? 24u : 32u) : 16u;
         p.maskMode[eye] = classify_mask(p.centre[eye], p.radius[1], ow, oh, gw, gh);
+    }
+    if (reuse) {
+        std::memcpy(p.centre, reuse->centre, sizeof p.centre); std::memcpy(p.radius, reuse->radius, sizeof p.radius);
+        p.maskMode[0] = reuse->maskMode[0]; p.maskMode[1] = reuse->maskMode[1];
+        p.maskGroupW = reuse->maskGroupW; p.maskGroupH = cfg.use_nis ? (scaleNotOne ? 24u : 32u) : 16u; // (a moved group height: a moved doUpscale)
     }
     if (cfg.use_nis) {
         // NVScalerUpdateConfig (scale != 1) or NVSharpenUpdateConfig (out == in), PostProcessor.cpp:308,:433
@@ -615,12 +616,13 @@ static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t
         easu_footprints(p);
         if (easu_lds_bytes(p.launchPrec, (int)pf, p.cellsW, p.cellsH) > 64 * 1024) return kRefusals[R_EASU_LDS];
     }
-    reciprocals(p);
+    if (reuse) { p.rcpOut[0] = reuse->rcpOut[0]; p.rcpOut[1] = reuse->rcpOut[1]; p.rcpExact = reuse->rcpExact; }
+    else reciprocals(p);
     if (p.doUpscale) tap_tables(p);
     p.maskLists = p.doUpscale && p.launchPrec == PREC_FP32 && (p.maskMode[0] == MASK_MIXED || p.maskMode[1] == MASK_MIXED);
     // a hidden-area mesh (header, ovrfsr_set_hidden_area): product arithmetic and an upscale stage, like the lists it is built on.  The lists
     // then exist whatever the mask; the FORM below is chosen from the mask alone -- an unmasked two-pass stays two-pass, launched over lists
-    p.hiddenArea = hidden && (hidden->triangles[0] || hidden->triangles[1]) && p.doUpscale && p.launchPrec == PREC_FP32;
+    p.hiddenArea = (reuse ? reuse->hiddenArea : hidden && (hidden->triangles[0] || hidden->triangles[1])) && p.doUpscale && p.launchPrec == PREC_FP32;
     p.tileLists = p.maskLists || p.hiddenArea;
     if (p.doSharpen && !cfg.use_nis) {
         float s = cfg.sharpness;
@@ -673,37 +675,93 @@ static Refusal plan_filtered(const ovrfsr_config &cfg, uint32_t format, uint32_t
     v.inW = (int32_t)width; v.inH = (int32_t)height; v.outW = (int32_t)ow; v.outH = (int32_t)oh;
     p.overlapOutside = p.maskLists && !(sorted && pf != OVRFSR_FORMAT_RGBA8_UNORM) && !outside_staged_ok(v, (int)pf);
 
-    HiddenMaps maps;
-    if (p.hiddenArea) maps = hidden_maps(p, *hidden);
-    if (gaze) {
+    if (reuse) { // the layout and the lists stay where they are: rescale_pipeline compares everything else
+        const PlanFields &r = *reuse;
+        p.gazeCapable = r.gazeCapable; p.rescaleCapable = r.rescaleCapable;
+        p.listRegion = r.listRegion; p.spanRegion = r.spanRegion;
+        p.listsShared = r.listsShared;
+        for (int eye = 0; eye < 2; ++eye) {
+            p.nInside[eye] = r.nInside[eye]; p.nOutside[eye] = r.nOutside[eye]; p.nRing[eye] = r.nRing[eye]; p.nSpans[eye] = r.nSpans[eye];
+            p.nRcas[eye] = r.nRcas[eye]; p.nSkipped[eye] = r.nSkipped[eye];
+            p.listOffInside[eye] = r.listOffInside[eye]; p.listOffOutside[eye] = r.listOffOutside[eye]; p.listOffRing[eye] = r.listOffRing[eye];
+            p.listOffRcas[eye] = r.listOffRcas[eye]; p.spanOff[eye] = r.spanOff[eye];
+        }
+        *plan = std::move(p);
+        return Refusal{};
+    }
+    HiddenMaps rasterised;
+    if (p.hiddenArea) rasterised = hidden_maps(p, *hidden);
+    if (maps) {
         p.gazeCapable = true;
+        p.rescaleCapable = rescaleCapable;
         gaze_regions(p);
     }
-    if (p.tileLists) tile_lists(p, maps, &p);
-    if (gaze) *gaze = std::move(maps);
+    if (p.tileLists) tile_lists(p, rasterised, &p);
+    if (maps) *maps = std::move(rasterised);
     *plan = std::move(p);
     return Refusal{};
 }
 
-Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden, int hdrDomain, HiddenMaps *gaze)
+// what plan_pipeline makes of the RGBA32F twin's plan under OVRFSR_HDR_DOMAIN_SRTM
+static void as_hdr_domain_plan(Plan &p, const ovrfsr_config &cfg, uint32_t format)
 {
     const uint32_t pf = pipeline_format(format);
+    p.hdrDomain = true;
+    p.inputFormat = format;                                                    // what the plan is FOR (PostProcessor::PlannedFor)
+    p.ownedFormat = cfg.reference_formats ? reference_output_format(pf) : pf;  // the submission's own rule
+    p.rcasPrec = p.launchPrec;                                                 // RCAS stores fp32 here: nothing for exact stores to guard
+}
+
+Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
+                      const HiddenArea *hidden, int hdrDomain, HiddenMaps *gaze, HiddenMaps *rescale)
+{
+    const uint32_t pf = pipeline_format(format);
+    HiddenMaps *const maps = rescale ? rescale : gaze; // one layout for both; the caller hands the same maps where it asks for both
     if (hdrDomain == OVRFSR_HDR_DOMAIN_SRTM && (pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F)) {
         // FSR 1's reversible tone-mapped domain (header, "HDR domain"): the pipeline is the RGBA32F submission's, between a forward pass that
         // writes its input and a back pass that reads its result, both ctx-owned RGBA32F images.  No mesh: the back pass walks whole images.
         Plan p;
-        if (!plan_filtered(cfg, OVRFSR_FORMAT_RGBA32F, width, height, onlyOneEye, &p, nullptr, gaze)) {
-            p.hdrDomain = true;
-            p.inputFormat = format;                                                    // what the plan is FOR (PostProcessor::PlannedFor)
-            p.ownedFormat = cfg.reference_formats ? reference_output_format(pf) : pf;  // the submission's own rule
-            p.rcasPrec = p.launchPrec;                                                 // RCAS stores fp32 here: nothing for exact stores to guard
+        if (!plan_filtered(cfg, OVRFSR_FORMAT_RGBA32F, width, height, onlyOneEye, &p, nullptr, maps, rescale != nullptr)) {
+            as_hdr_domain_plan(p, cfg, format);
             *plan = std::move(p);
             return Refusal{};
         }
         // (refused as RGBA32F: whatever the submission itself gets -- the same refusal, or its own plan with the setting not applied)
     }
-    return plan_filtered(cfg, format, width, height, onlyOneEye, plan, hidden, gaze);
+    return plan_filtered(cfg, format, width, height, onlyOneEye, plan, hidden, maps, rescale != nullptr);
+}
+
+Rescale rescale_pipeline(const Plan &current, const ovrfsr_config &effective, uint32_t width, uint32_t height, const HiddenMaps &hidden,
+                         int hdrDomain, Plan *rescaled)
+{
+    (void)hidden; // (the lists stay as they are: nothing here classifies a tile)
+    const PlanFields &c = current;
+    if (width == c.inputWidth && height == c.inputHeight) return Rescale::Nothing;
+    if (!c.rescaleCapable) return Rescale::Rebuild;
+    // the RGBA32F twin of OVRFSR_HDR_DOMAIN_SRTM: in place only where `current` is that twin's plan and the new size's is too
+    const uint32_t pf = pipeline_format(c.inputFormat);
+    const bool wantsTwin = hdrDomain == OVRFSR_HDR_DOMAIN_SRTM && (pf == OVRFSR_FORMAT_RGBA16F || pf == OVRFSR_FORMAT_RGBA32F);
+    if (wantsTwin != c.hdrDomain) return Rescale::Rebuild;
+    Plan p;
+    if (plan_filtered(effective, c.hdrDomain ? (uint32_t)OVRFSR_FORMAT_RGBA32F : c.inputFormat, width, height, c.onlyOneEye, &p, nullptr, nullptr, true, &c))
+        return Rescale::Rebuild; // (a refusal: the rebuild fails as a fresh ctx does)
+    if (c.hdrDomain) as_hdr_domain_plan(p, effective, c.inputFormat);
+    // everything plan_filtered computed that a re-scale must not move (the mask, the reciprocals, the layout and the lists were taken over)
+    const bool same = p.inputFormat == c.inputFormat && p.onlyOneEye == c.onlyOneEye && p.outputWidth == c.outputWidth && p.outputHeight == c.outputHeight &&
+                      p.doUpscale == c.doUpscale && p.doSharpen == c.doSharpen && p.useNis == c.useNis && p.form == c.form && p.tileLists == c.tileLists &&
+                      p.maskLists == c.maskLists && p.hiddenArea == c.hiddenArea && p.overlapOutside == c.overlapOutside && p.hdrDomain == c.hdrDomain &&
+                      p.pipelineFormat == c.pipelineFormat && p.intermediateFormat == c.intermediateFormat && p.ownedFormat == c.ownedFormat &&
+                      p.launchPrec == c.launchPrec && p.rcasPrec == c.rcasPrec && !std::memcmp(p.rcasCon, c.rcasCon, sizeof p.rcasCon) &&
+                      !std::memcmp(&p.tieHalfMin, &c.tieHalfMin, sizeof(float)) && !std::memcmp(&p.unorm8StoreGuard, &c.unorm8StoreGuard, sizeof(float)) &&
+                      p.tapYOff == c.tapYOff && p.maskGroupH == c.maskGroupH && p.grid.tileW == c.grid.tileW && p.grid.tileH == c.grid.tileH &&
+                      p.grid.groupW == c.grid.groupW && p.grid.groupH == c.grid.groupH && p.grid.tx == c.grid.tx && p.grid.ty == c.grid.ty;
+    if (!same) return Rescale::Rebuild;
+    if (p.tileLists && !current.lists.empty()) {
+        p.lists = current.lists; p.spans = current.spans;
+        p.recs = outside_records(p, p);
+    }
+    *rescaled = std::move(p);
+    return Rescale::InPlace;
 }
 
 Reaim reaim_pipeline(const Plan &current, const ovrfsr_config &effective, const HiddenMaps &hidden, Plan *reaimed, bool hostRecords)

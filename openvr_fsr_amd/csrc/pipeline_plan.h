@@ -114,6 +114,10 @@ struct PlanFields {
     bool gazeCapable = false;
     size_t listRegion = 0, spanRegion = 0;
     uint32_t maskGroupW = 0, maskGroupH = 0;
+    // A rescale-capable plan (plan_pipeline, `rescale`; header, "Dynamic resolution"): planned in the gaze layout above -- the lists stay
+    // resident in their regions and tile_records_kernel addresses every entry's record --, so that rescale_pipeline's result needs nothing
+    // but new constants, new tap tables and a records pass
+    bool rescaleCapable = false;
 };
 
 struct Plan : PlanFields {
@@ -154,8 +158,11 @@ int plan_output_size(const ovrfsr_config &cfg, uint32_t inW, uint32_t inH, uint3
 // `gaze`: non-null plans a GAZE-CAPABLE plan (a gaze is set on either eye: ovrfsr_set_gaze; `cfg` is the effective configuration, the gazes
 // in proj_centre) -- the same plan in every field but the list and span offsets, laid out in per-eye regions (PlanFields::gazeCapable) --
 // and leaves the rasterised hidden-area maps there for reaim_pipeline.
+// `rescale`: non-null plans a RESCALE-CAPABLE plan (a maximum input size is set: ovrfsr_set_max_input_size) -- the same plan in every field
+// the kernels read, in the gaze layout whether or not a gaze is set (PlanFields::rescaleCapable), the maps left there like `gaze`'s.
 Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width, uint32_t height, bool onlyOneEye, Plan *plan,
-                      const HiddenArea *hidden = nullptr, int hdrDomain = OVRFSR_HDR_DOMAIN_LINEAR, HiddenMaps *gaze = nullptr);
+                      const HiddenArea *hidden = nullptr, int hdrDomain = OVRFSR_HDR_DOMAIN_LINEAR, HiddenMaps *gaze = nullptr,
+                      HiddenMaps *rescale = nullptr);
 
 // The re-aim step (header, "Eye-tracked foveation"): what becomes of `current` when only proj_centre moved -- `effective` is the configuration
 // `current` was planned from with the gazes of the moment in proj_centre, `hidden` what plan_pipeline left in `gaze`.  Pure; re-runs
@@ -168,6 +175,21 @@ Refusal plan_pipeline(const ovrfsr_config &cfg, uint32_t format, uint32_t width,
 //             inside the radius, which resolve_in_staging decides by; or `current` is not gaze-capable: plan afresh.  *reaimed is not written
 enum class Reaim { Nothing, InPlace, Rebuild };
 Reaim reaim_pipeline(const Plan &current, const ovrfsr_config &effective, const HiddenMaps &hidden, Plan *reaimed, bool hostRecords = true);
+
+// The re-scale step (header, "Dynamic resolution"): what becomes of `current` when only the input size moved -- `effective` and `hdrDomain`
+// are what `current` was planned from, `hidden` what plan_pipeline left in `rescale` (the lists stay, so the maps are not read).  Pure; re-runs
+// the constants, the footprints, the refusals, the form rule and the tap tables for the new size, never the mesh rasteriser, reciprocals,
+// the mask classification or the tile lists.
+//   Nothing   the size is the planned one: *rescaled is not written
+//   InPlace   plan_pipeline at the new size differs from `current` in inputWidth / inputHeight, easuCon, cells*, fusedCells*, nis, nisCells*,
+//             the tap tables with outsideCols / outsideRows and the records only: *rescaled is that plan -- with the lists, spans and
+//             host-built records where `current` still holds its lists, else without the three (the launch manager's lists are on the
+//             device, where tile_records_kernel rebuilds the records)
+//   Rebuild   anything else would move (the output size, doUpscale, the form, tileLists, maskLists, overlapOutside, a format), the fresh plan
+//             is a refusal, or `current` is not rescale-capable: plan afresh.  *rescaled is not written
+enum class Rescale { Nothing, InPlace, Rebuild };
+Rescale rescale_pipeline(const Plan &current, const ovrfsr_config &effective, uint32_t width, uint32_t height, const HiddenMaps &hidden,
+                         int hdrDomain, Plan *rescaled);
 
 // what depends on the destination the call names
 Refusal destination_refusal(const Plan &plan, uint32_t destFormat);

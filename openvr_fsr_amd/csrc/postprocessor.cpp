@@ -45,6 +45,15 @@ static bool inject_failure() { return g_fail_countdown > 0 && --g_fail_countdown
 #else
 static inline bool inject_failure() { return false; }
 #endif
+// checked builds can switch the route a re-scale refills the tap tables by at run time (tests/test_gpu_dynamic_resolution.py compares the
+// two); everywhere else it is the build's constant
+#ifdef OVRFSR_BOUNDS
+static bool g_upload_taps = false;
+void debug_tap_route(int upload) { g_upload_taps = upload != 0; }
+static inline bool upload_taps(bool) { return g_upload_taps; }
+#else
+static inline bool upload_taps(bool byBuild) { return byBuild; }
+#endif
 static inline hipError_t dev_malloc(void **p, size_t bytes) { return inject_failure() ? hipErrorOutOfMemory : hipMalloc(p, bytes); }
 static inline hipError_t host_malloc(void **p, size_t bytes) { return inject_failure() ? hipErrorOutOfMemory : hipHostMalloc(p, bytes, hipHostMallocDefault); }
 static inline hipError_t event_create(hipEvent_t *e, unsigned flags) { return inject_failure() ? hipErrorOutOfMemory : hipEventCreateWithFlags(e, flags); }
@@ -249,6 +258,17 @@ int PostProcessor::SetHdrDomain(int domain)
     return OVRFSR_OK;
 }
 
+// ovrfsr_set_max_input_size behind its argument checks: the value, and what SetHdrDomain does -- no device resource is touched here, the
+// next apply resets and plans afresh (rescale-capable where a maximum is set), refused under capture as any build is.  Reset keeps the value.
+int PostProcessor::SetMaxInputSize(uint32_t width, uint32_t height)
+{
+    maxInput_[0] = width; maxInput_[1] = height;
+    sequence_.Reset(true);
+    enabled_ = true;
+    replan_ = true;
+    return OVRFSR_OK;
+}
+
 int PostProcessor::HiddenAreaStats(int eye, uint32_t *tilesTotal, uint32_t *tilesSkipped)
 {
     if (!initialized_ || replan_) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "no plan yet: hidden-area statistics follow a successful apply");
@@ -292,6 +312,13 @@ int PostProcessor::EnsureBuffer(DeviceBuffer &buf, size_t need)
 // The tile lists of a gaze-capable plan: the device tables sized by the plan's regions, the staging ring and its events (created here, at
 // build time, so that a re-aim creates nothing), then the first upload the way every later one goes -- through a staging slot on the caller's
 // stream, the records built behind it by tile_records_kernel.
+int PostProcessor::BuildStagingRing()
+{
+    hipError_t e = host_malloc(reinterpret_cast<void **>(&gazeStage_), kGazeSlots * GazeSlotDwords() * sizeof(uint32_t));
+    for (int i = 0; i < kGazeSlots && e == hipSuccess; ++i) e = event_create(&gazeEvent_[i], hipEventDisableTiming);
+    return e == hipSuccess ? OVRFSR_OK : BuildFailed(e, "gaze staging ring: ");
+}
+
 int PostProcessor::BuildGazeTables(hipStream_t stream)
 {
     const size_t listDwords = 2 * plan_.listRegion, spanDwords = 4 * plan_.spanRegion; // (listRegion is a multiple of 4: the records are 16-byte aligned)
@@ -299,10 +326,9 @@ int PostProcessor::BuildGazeTables(hipStream_t stream)
     if (e != hipSuccess) return BuildFailed(e, "tile lists: ");
     tileRecDev_ = tileListDev_ + listDwords;
     spanRecDev_ = spanDwords ? tileRecDev_ + 4 * listDwords : nullptr;
-    e = host_malloc(reinterpret_cast<void **>(&gazeStage_), kGazeSlots * GazeSlotDwords() * sizeof(uint32_t));
-    for (int i = 0; i < kGazeSlots && e == hipSuccess; ++i) e = event_create(&gazeEvent_[i], hipEventDisableTiming);
-    if (e != hipSuccess) return BuildFailed(e, "gaze staging ring: ");
-    const int rc = UploadGazeLists(plan_, stream);
+    int rc = BuildStagingRing();
+    if (rc != OVRFSR_OK) return rc;
+    rc = UploadGazeLists(plan_, stream);
     for (std::vector<uint32_t> *v : {&plan_.lists, &plan_.recs, &plan_.spans}) std::vector<uint32_t>().swap(*v);
     return rc;
 }
@@ -310,6 +336,23 @@ int PostProcessor::BuildGazeTables(hipStream_t stream)
 // `from`: a gaze-capable plan's lists and spans in its regions, with the counts and offsets plan_ has by now.  What each eye's region uses
 // goes into the next staging slot -- after the event behind that slot's last copies: a host wait only where the ring is full -- and from
 // there to the device on the caller's stream; then the records of those entries.  Nothing is allocated, nothing blocks.
+// every entry the plan's per-eye regions use, with the tap tables and the footprint caps of the moment
+TileRecordsArgs PostProcessor::RecordsArgs() const
+{
+    TileRecordsArgs ta;
+    ta.lists = tileListDev_; ta.recs = tileRecDev_;
+    ta.bilX = bilinDev_; ta.bilY = bilinDev_ + plan_.tapYOff;
+    ta.g = record_grid(plan_);
+    ta.regionEntries = (uint32_t)plan_.listRegion;
+    for (int eye = 0; eye < 2; ++eye) {
+        const size_t base = (size_t)eye * plan_.listRegion; // == listOffInside[eye]
+        const size_t end = std::max(std::max(plan_.listOffRing[eye] + plan_.nRing[eye], plan_.listOffOutside[eye] + plan_.nOutside[eye]),
+                                    plan_.listOffRcas[eye] + plan_.nRcas[eye]);
+        ta.n[eye] = (uint32_t)(end - base);
+    }
+    return ta;
+}
+
 int PostProcessor::UploadGazeLists(const Plan &from, hipStream_t stream)
 {
     const int slot = gazeSlot_;
@@ -317,16 +360,10 @@ int PostProcessor::UploadGazeLists(const Plan &from, hipStream_t stream)
     hipError_t e = gazeSlotUsed_[slot] ? hipEventSynchronize(gazeEvent_[slot]) : hipSuccess;
     uint32_t *host = gazeStage_ + (size_t)slot * GazeSlotDwords(), *hostSpans = host + 2 * plan_.listRegion;
     uint32_t *hostRecs = hostSpans + 4 * plan_.spanRegion; // (kGazeHostRecords only)
-    TileRecordsArgs ta;
-    ta.lists = tileListDev_; ta.recs = tileRecDev_;
-    ta.bilX = bilinDev_; ta.bilY = bilinDev_ + plan_.tapYOff;
-    ta.g = record_grid(plan_);
-    ta.regionEntries = (uint32_t)plan_.listRegion;
+    const TileRecordsArgs ta = RecordsArgs();
     for (int eye = 0; eye < 2 && e == hipSuccess; ++eye) {
         const size_t base = (size_t)eye * plan_.listRegion; // == listOffInside[eye]
-        const size_t end = std::max(std::max(plan_.listOffRing[eye] + plan_.nRing[eye], plan_.listOffOutside[eye] + plan_.nOutside[eye]),
-                                    plan_.listOffRcas[eye] + plan_.nRcas[eye]);
-        const size_t n = ta.n[eye] = (uint32_t)(end - base);
+        const size_t n = ta.n[eye];
         if (n) {
             std::memcpy(host + base, from.lists.data() + base, n * sizeof(uint32_t));
             e = hipMemcpyAsync(tileListDev_ + base, host + base, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
@@ -376,6 +413,60 @@ int PostProcessor::AimGaze(hipStream_t stream)
     return rc;
 }
 
+// The re-scale step of an apply (header, "Dynamic resolution").  Is `in` the planned submission at another size, on a ctx with a maximum set?
+bool PostProcessor::SizeMoved(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const
+{
+    return maxInput_[0] != 0 && initialized_ && !replan_ && in.format == plan_.inputFormat && (!compareEyeLayout || plan_.onlyOneEye == onlyOneEye) &&
+           (in.width != plan_.inputWidth || in.height != plan_.inputHeight);
+}
+
+// `rescaled`: rescale_pipeline's InPlace answer.  Its fields and tap tables take the current ones' place; the device tables follow on the
+// caller's stream -- the taps by tap_tables_kernel (or, the measurement build's route, through the next staging slot: a host wait only where
+// the ring is full), then the records of every list entry, which depend on the taps and the footprint caps.  Nothing is allocated, nothing
+// blocks, and the images the ctx owns stay where they are; the launches behind read the new constants from plan_.
+int PostProcessor::RescaleInPlace(Plan &rescaled, hipStream_t stream)
+{
+    static_cast<PlanFields &>(plan_) = rescaled;
+    plan_.taps.swap(rescaled.taps);
+    hipError_t e = hipSuccess;
+    if (upload_taps(kRescaleUploadTaps)) {
+        const int slot = gazeSlot_;
+        gazeSlot_ = (slot + 1) % kGazeSlots;
+        if (gazeSlotUsed_[slot]) e = hipEventSynchronize(gazeEvent_[slot]);
+        uint32_t *host = gazeStage_ + (size_t)slot * GazeSlotDwords() + GazeSlotTapsAt();
+        const size_t bytes = plan_.taps.size() * sizeof(BilinTap);
+        std::memcpy(host, plan_.taps.data(), bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(bilinDev_, host, bytes, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipEventRecord(gazeEvent_[slot], stream);
+        gazeSlotUsed_[slot] = true;
+        if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("tap table upload: ") + hipGetErrorString(e));
+    } else {
+        TapTablesArgs ta;
+        ta.taps = bilinDev_;
+        ta.outW = plan_.outputWidth; ta.outH = plan_.outputHeight; ta.inW = plan_.inputWidth; ta.inH = plan_.inputHeight;
+        ta.tapYOff = plan_.tapYOff;
+        const int rc = Launched(launch_tap_tables(ta, stream), "tap tables");
+        if (rc != OVRFSR_OK) return rc;
+    }
+    if (plan_.tileLists) {
+        const int rc = Launched(launch_tile_records(RecordsArgs(), stream), "tile records");
+        if (rc != OVRFSR_OK) return rc;
+    }
+    ++rescales_;
+    return OVRFSR_OK;
+}
+
+#ifdef OVRFSR_BOUNDS
+int PostProcessor::DebugReadTaps(void *dst, size_t bytes)
+{
+    DeviceGuard guard(device_);
+    if (!initialized_ || !bilinDev_ || bytes != plan_.taps.size() * sizeof(BilinTap)) return Fail(OVRFSR_ERR_INVALID_ARGUMENT, "no tap tables of that size");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(dst, bilinDev_, bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? OVRFSR_OK : Fail(OVRFSR_ERR_HIP, std::string("tap table read-back: ") + hipGetErrorString(e));
+}
+#endif
+
 // The destination refusals that count as a failed build (exact stores: the sharpen stage's destination must be RGBA8 too): known only once
 // the call names its `out`, they disable the ctx.  The others (destination_refusal) are ApplyPostProcess's: a pair_submit first eye is
 // recorded with such a destination and refused when it is launched.
@@ -415,8 +506,10 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneE
     // with a gaze set on either eye the plan is made from the gazes and laid out for re-aiming (Plan::gazeCapable); without one: as ever
     const bool gazeCapable = gazeSet_[0] || gazeSet_[1];
     gazeMoved_ = false; // (this plan is aimed at the gazes of the moment)
+    // with a maximum input size set it is laid out the same way and keeps what a re-scale needs (Plan::rescaleCapable)
+    const bool rescaleCapable = maxInput_[0] != 0;
     const Refusal refused = plan_pipeline(EffectiveConfig(), submitted.format, submitted.width, submitted.height, onlyOneEye, &plan_, &hidden, hdrDomain_,
-                                          gazeCapable ? &hiddenMaps_ : nullptr);
+                                          gazeCapable ? &hiddenMaps_ : nullptr, rescaleCapable ? &hiddenMaps_ : nullptr);
     if (refused) return Fail(refused.status, refused.text);
     if (plan_.useNis) { // coef_scale[512] | coef_usm[512], PostProcessor.cpp:366-382
         hipError_t e = dev_malloc(reinterpret_cast<void **>(&nisCoefDev_), 2 * 512 * sizeof(float));
@@ -448,6 +541,19 @@ int PostProcessor::PrepareResources(const ovrfsr_image &submitted, bool onlyOneE
         if (e != hipSuccess) return Fail(OVRFSR_ERR_HIP, std::string("tile lists: ") + hipGetErrorString(e));
         // the host copies have served (several MB at 16384^2); the per-call path reads the plan's counts and offsets only
         for (std::vector<uint32_t> *v : {&plan_.lists, &plan_.recs, &plan_.spans}) std::vector<uint32_t>().swap(*v);
+    }
+    if (plan_.rescaleCapable && plan_.doUpscale) {
+        // what a later re-scale would otherwise create: the staging ring where the tile lists did not bring it, and the front passes' copies
+        // and the HDR domain's mapped copy at the maximum input size (one image; a larger batch grows them as ever)
+        int rc = plan_.tileLists ? OVRFSR_OK : BuildStagingRing();
+        const uint32_t base = base_format(submitted.format), samples = format_samples(submitted.format);
+        const size_t mw = maxInput_[0], mh = maxInput_[1];
+        if (rc == OVRFSR_OK && (samples > 1u || base == OVRFSR_FORMAT_R11G11B10F))
+            rc = EnsureBuffer(resolved_, SizedForMax(0, (size_t)resolve_pitch((int)base, (uint32_t)mw) * mh));
+        else if (rc == OVRFSR_OK && submitted.format == OVRFSR_FORMAT_BGRA8_UNORM)
+            rc = EnsureBuffer(swizzled_, SizedForMax(0, mw * mh * texel_bytes(OVRFSR_FORMAT_RGBA8_UNORM)));
+        if (rc == OVRFSR_OK && plan_.hdrDomain && plan_.form != Form::None) rc = EnsureBuffer(hdrIn_, SizedForMax(0, mw * mh * 16u));
+        if (rc != OVRFSR_OK) return rc;
     }
     if (cfg_.debug_mode) {
         // every slot is checked on its own: a creation that failed half-way through the ring (found by fault injection, round 6: slot 0 existed,
@@ -766,7 +872,7 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
         in.format = pipeline_format(submitted.format);
         in.pitch_bytes = resolve_pitch((int)base, in.width);
         inStride = (size_t)in.pitch_bytes * in.height;
-        int rc = EnsureBuffer(resolved_, inStride * n);
+        int rc = EnsureBuffer(resolved_, SizedForMax(inStride, (size_t)resolve_pitch((int)base, maxInput_[0]) * maxInput_[1]) * n);
         if (rc != OVRFSR_OK) return rc;
         in.data = resolved_.p;
         // the debug-mode timer brackets the resolve too (header: unlike the reference's query, which starts after ResolveSubresource)
@@ -781,7 +887,7 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
             in.format = pipeline_format(submitted.format);
             in.pitch_bytes = in.width * texel_bytes(in.format);
             inStride = (size_t)in.pitch_bytes * in.height;
-            int rc = EnsureBuffer(swizzled_, inStride * n);
+            int rc = EnsureBuffer(swizzled_, SizedForMax(inStride, (size_t)maxInput_[0] * maxInput_[1] * texel_bytes(in.format)) * n);
             if (rc != OVRFSR_OK) return rc;
             in.data = swizzled_.p;
             rc = Launched(launch_bgra_to_rgba(static_cast<const uint8_t *>(submitted.data), submitted.pitch_bytes, submittedStride,
@@ -802,7 +908,7 @@ int PostProcessor::ApplyPostProcess(uint32_t n, int firstEye, int alternate, con
         pipeOut.format = OVRFSR_FORMAT_RGBA32F;
         pipeOut.pitch_bytes = out.width * 16u;
         pipeOutStride = (size_t)pipeOut.pitch_bytes * out.height;
-        int rc = EnsureBuffer(hdrIn_, mappedStride * n);
+        int rc = EnsureBuffer(hdrIn_, SizedForMax(mappedStride, (size_t)maxInput_[0] * maxInput_[1] * 16u) * n);
         if (rc == OVRFSR_OK) rc = EnsureBuffer(hdrOut_, pipeOutStride * n);
         if (rc != OVRFSR_OK) return rc;
         rc = Launched(launch_hdr_forward((int)in.format, static_cast<const uint8_t *>(in.data), in.pitch_bytes, inStride, static_cast<uint8_t *>(hdrIn_.p),
@@ -885,6 +991,21 @@ int PostProcessor::EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &i
     if (gazeMoved_ && initialized_ && !replan_ && (PlannedFor(in, onlyOneEye, compareEyeLayout) || sequence_.state().havePending)) rc = AimGaze(stream);
     if (rc == OVRFSR_OK && recorded == Recorded::GoesFirst) rc = FlushPending(stream);
     if (rc != OVRFSR_OK) return rc;
+    // the re-scale step (header, "Dynamic resolution"): the planned submission at another size, on a ctx with a maximum.  In place: a recorded
+    // eye is launched first, at its own size (nothing is freed, so no image is retired); then the new constants and tables; then the gaze,
+    // if it moved too -- the records depend on both.  Anything else is the rebuild below, counted.
+    const bool sizeMoved = SizeMoved(in, onlyOneEye, compareEyeLayout);
+    if (sizeMoved && in.width <= maxInput_[0] && in.height <= maxInput_[1]) {
+        Plan rescaled;
+        if (rescale_pipeline(plan_, EffectiveConfig(), in.width, in.height, hiddenMaps_, hdrDomain_, &rescaled) == Rescale::InPlace) {
+            if (recorded == Recorded::OnChange) rc = FlushPending(stream);
+            if (rc != OVRFSR_OK) return rc;
+            rc = RescaleInPlace(rescaled, stream);
+            if (rc == OVRFSR_OK && gazeMoved_) rc = AimGaze(stream);
+            if (rc != OVRFSR_OK) enabled_ = false; // as a failed (re)build: disabled until reset
+            return rc;
+        }
+    }
     if (initialized_ && !PlannedFor(in, onlyOneEye, compareEyeLayout)) {
         bool retire = false; // the recorded eye belongs to the old resources
         if (recorded == Recorded::OnChange) rc = FlushPending(stream, &retire);
@@ -898,6 +1019,7 @@ int PostProcessor::EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &i
     if (!initialized_) {
         rc = PrepareResources(in, onlyOneEye, stream); // :146
         if (rc != OVRFSR_OK) enabled_ = false; // :148-151
+        else if (sizeMoved) ++sizeRebuilds_;
     }
     return rc;
 }

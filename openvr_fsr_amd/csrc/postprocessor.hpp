@@ -16,6 +16,7 @@ namespace ovrfsr {
 
 #ifdef OVRFSR_BOUNDS
 void debug_fail_resource(int nth); // checked builds: the nth device allocation / stream / event creation from now on fails, once (postprocessor.cpp)
+void debug_tap_route(int upload);  // checked builds: a re-scale refills the tap tables by upload (1) or by tap_tables_kernel (0), from now on
 #endif
 
 // a device allocation that knows its size
@@ -53,6 +54,14 @@ public:
     void ClearGaze(int eye);
     void GetGaze(int eye, float xy[2], int *isSet) const;
     void GazeStats(uint32_t *reaims, uint32_t *rebuilds) const { *reaims = reaims_; *rebuilds = rebuilds_; }
+    // ovrfsr_set_max_input_size / ovrfsr_get_max_input_size / ovrfsr_rescale_stats behind their argument checks.  The setter stores the value
+    // and does what SetHdrDomain does: the next apply plans afresh, rescale-capable where a maximum is set (EnsurePlanned -> RescaleInput)
+    int SetMaxInputSize(uint32_t width, uint32_t height);
+    void MaxInputSize(uint32_t *width, uint32_t *height) const { *width = maxInput_[0]; *height = maxInput_[1]; }
+    void RescaleStats(uint32_t *rescales, uint32_t *rebuilds) const { *rescales = rescales_; *rebuilds = sizeRebuilds_; }
+#ifdef OVRFSR_BOUNDS
+    int DebugReadTaps(void *dst, size_t bytes); // checked builds: the device tap tables as they are once the stream work so far is done
+#endif
     int LastGpuTimeMs(float *ms);
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
@@ -69,6 +78,11 @@ private:
     bool gazeMoved_ = false;
     uint32_t reaims_ = 0, rebuilds_ = 0;
     ovrfsr_config EffectiveConfig() const; // cfg_ with the gazes that are set in proj_centre: what the plan is made from
+    // ovrfsr_set_max_input_size's value ({0, 0}: none): outlives Reset and SetConfig like the three above.  With one set the plan is
+    // rescale-capable (Plan::rescaleCapable) and the buffers sized by the input are sized by the maximum.  rescales_ / sizeRebuilds_: the
+    // applies whose input size differed from the planned one and that re-scaled in place / rebuilt, since create
+    uint32_t maxInput_[2] = {0, 0};
+    uint32_t rescales_ = 0, sizeRebuilds_ = 0;
 
     // PostProcessor.h:16-24
     bool enabled_ = true;
@@ -102,10 +116,27 @@ private:
 #else
     static constexpr bool kGazeHostRecords = false;
 #endif
-    size_t GazeSlotDwords() const { return (kGazeHostRecords ? 10 : 2) * plan_.listRegion + 4 * plan_.spanRegion; }
+    // (a rescale-capable plan: the tap tables behind them, for the upload route of a re-scale -- 2 dwords per tap)
+    size_t GazeSlotTapsAt() const { return (kGazeHostRecords ? 10 : 2) * plan_.listRegion + 4 * plan_.spanRegion; }
+    size_t GazeSlotDwords() const { return GazeSlotTapsAt() + (plan_.rescaleCapable ? 2 * plan_.taps.size() : 0); }
+#ifdef OVRFSR_RESCALE_UPLOAD_TAPS /* measurement build (never shipped): a re-scale uploads the host-built tap tables through a staging slot
+                                     instead of running tap_tables_kernel -- the other side of the comparison in profiles/dynamic_resolution.txt */
+    static constexpr bool kRescaleUploadTaps = true;
+#else
+    static constexpr bool kRescaleUploadTaps = false;
+#endif
     void FreeTables();                    // the plan's tables on the device and the staging ring
     int BuildFailed(hipError_t e, const char *what); // a creation or upload of PrepareResources failed
+    int BuildStagingRing();                           // the pinned ring and its events
     int BuildGazeTables(hipStream_t stream);          // PrepareResources' part for the tile lists of a gaze-capable plan
+    TileRecordsArgs RecordsArgs() const;              // tile_records_kernel over every list entry in use
+    // EnsurePlanned's re-scale step (header, "Dynamic resolution"): is this input the planned one at another size, on a ctx with a maximum?
+    // Then *step is the planner's answer and, for InPlace, *rescaled the plan RescaleInPlace puts in plan_'s place
+    bool SizeMoved(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const;
+    int RescaleInPlace(Plan &rescaled, hipStream_t stream);
+    // one image of a buffer sized by the input (resolved_, swizzled_, hdrIn_): `now` bytes for the submission, `atMax` for the maximum input
+    // size -- what a rescale-capable ctx allocates, so that no later size within the maximum grows it
+    size_t SizedForMax(size_t now, size_t atMax) const { return plan_.rescaleCapable && atMax > now ? atMax : now; }
     int UploadGazeLists(const Plan &from, hipStream_t stream); // lists and spans through the next staging slot, then the records
     int AimGaze(hipStream_t stream);      // EnsurePlanned's gaze step: nothing, a re-aim in place, or a rebuild of the tables
     // the memory-bound outside-tile kernel and the VALU-bound inside-tile kernel are independent: the former runs on

@@ -164,6 +164,23 @@ class PostProcessor:
         self._check_arg(self._lib.ovrfsr_gaze_stats(self._ctx, C.byref(reaims), C.byref(rebuilds)), "ovrfsr_gaze_stats")
         return reaims.value, rebuilds.value
 
+    def set_max_input_size(self, max_width, max_height):
+        """ovrfsr_set_max_input_size: the largest input the ctx will see (the eye texture's allocation); (0, 0) clears it.  With one set, an
+        apply whose input size differs from the planned one re-scales in place where only the input size moved."""
+        self._check_arg(self._lib.ovrfsr_set_max_input_size(self._ctx, int(max_width), int(max_height)), "ovrfsr_set_max_input_size")
+
+    def max_input_size(self):
+        """ovrfsr_get_max_input_size: (max_width, max_height), (0, 0) where none is set."""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check_arg(self._lib.ovrfsr_get_max_input_size(self._ctx, C.byref(w), C.byref(h)), "ovrfsr_get_max_input_size")
+        return w.value, h.value
+
+    def rescale_stats(self):
+        """ovrfsr_rescale_stats: (re-scales in place, rebuilds) applies performed because of an input-size change while a maximum was set."""
+        rescales, rebuilds = C.c_uint32(), C.c_uint32()
+        self._check_arg(self._lib.ovrfsr_rescale_stats(self._ctx, C.byref(rescales), C.byref(rebuilds)), "ovrfsr_rescale_stats")
+        return rescales.value, rebuilds.value
+
     def _check_arg(self, rc, what):
         if rc != 0:  # (an argument check of the C ABI: it leaves ovrfsr_last_error alone)
             raise K.OvrFsrError(rc, what)
