@@ -77,4 +77,18 @@ inline uint32_t resolve_pitch(int fmt, uint32_t w)
     return (w * texel_bytes(pipeline_format((uint32_t)fmt)) + 15u) & ~15u;
 }
 
+// The launch manager's own copies of its input, and the bytes of ONE image of each for a submission of (fmt, w, h) -- 64-bit: the mapped
+// copy of a 16384 x 16384 image is 4 GiB.  The build (at the maximum input size) and the per-call path size the copies by this and nothing else.
+enum class InputCopy {
+    Resolved,  // the resolve / unpack pass's destination: single-sample texels of pipeline_format, rows of resolve_pitch
+    Reordered, // the BGRA8 re-order's destination: RGBA8, tight
+    Mapped     // the HDR domain's forward map: RGBA32F, tight
+};
+inline uint64_t input_copy_bytes(InputCopy copy, uint32_t fmt, uint32_t w, uint32_t h)
+{
+    return copy == InputCopy::Resolved  ? (uint64_t)resolve_pitch((int)base_format(fmt), w) * h
+         : copy == InputCopy::Reordered ? (uint64_t)w * h * texel_bytes(OVRFSR_FORMAT_RGBA8_UNORM)
+                                        : (uint64_t)w * h * 16u;
+}
+
 } // namespace ovrfsr

@@ -9,6 +9,7 @@
 #include "../../include/openvr_fsr_amd.h"
 #include "fsr_params.h"
 #include "nis_tables.h"
+#include "fsr_sizes.h"
 #include "pipeline_plan.h"
 #include "submit_sequence.h"
 
@@ -66,6 +67,22 @@ public:
     int AverageGpuTimeMs(float *ms, uint32_t *reports);
 
 private:
+    // What one apply hands from function to function, as values (plain aggregates: nothing computed, nothing owned).
+    // A call: what every launch of one apply shares.
+    struct Call { uint32_t n; int firstEye; int alternate; hipStream_t stream; };
+    // An image run: image 0 of a call's n images and the byte distance to the next one -- taken modulo 2^64 (at_offset, postprocessor.cpp);
+    // a run of one image has stride 0.
+    struct ImageRun {
+        ovrfsr_image first;
+        size_t stride;
+        // the tight run in `data`: images of w x h texels of `format`, rows `pitch` bytes apart, image after image
+        static ImageRun Tight(void *data, uint32_t format, uint32_t w, uint32_t h, uint32_t pitch) { return {{data, w, h, pitch, format}, (size_t)pitch * h}; }
+    };
+    // What is asked for: the (canonical) image 0 of the submission, and whether its images hold one eye each.  compareEyeLayout: a batch call
+    // also asks whether the plan assumes the same (Apply does not: PostProcessor::PlannedFor)
+    struct Asked { ovrfsr_image in; bool onlyOneEye; bool compareEyeLayout; };
+    static BatchView make_view(const ImageRun &from, const ImageRun &to); // what the kernels take of the two runs
+
     int device_;
     ovrfsr_config cfg_;
     std::string lastError_;
@@ -132,11 +149,16 @@ private:
     TileRecordsArgs RecordsArgs() const;              // tile_records_kernel over every list entry in use
     // EnsurePlanned's re-scale step (header, "Dynamic resolution"): is this input the planned one at another size, on a ctx with a maximum?
     // Then *step is the planner's answer and, for InPlace, *rescaled the plan RescaleInPlace puts in plan_'s place
-    bool SizeMoved(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const;
+    bool SizeMoved(const Asked &asked) const;
     int RescaleInPlace(Plan &rescaled, hipStream_t stream);
-    // one image of a buffer sized by the input (resolved_, swizzled_, hdrIn_): `now` bytes for the submission, `atMax` for the maximum input
-    // size -- what a rescale-capable ctx allocates, so that no later size within the maximum grows it
-    size_t SizedForMax(size_t now, size_t atMax) const { return plan_.rescaleCapable && atMax > now ? atMax : now; }
+    // one image of a ctx-owned copy of the input (resolved_, swizzled_, hdrIn_: input_copy_bytes, fsr_sizes.h) for a submission of
+    // (format, w, h) -- or, where that is more, for the maximum input size: what a rescale-capable ctx allocates, so that no later size within
+    // the maximum grows it.  PrepareResources asks with the maximum itself
+    size_t SizedForMax(InputCopy copy, uint32_t format, uint32_t w, uint32_t h) const
+    {
+        const uint64_t now = input_copy_bytes(copy, format, w, h), atMax = plan_.rescaleCapable ? input_copy_bytes(copy, format, maxInput_[0], maxInput_[1]) : 0;
+        return (size_t)(atMax > now ? atMax : now);
+    }
     int UploadGazeLists(const Plan &from, hipStream_t stream); // lists and spans through the next staging slot, then the records
     int AimGaze(hipStream_t stream);      // EnsurePlanned's gaze step: nothing, a re-aim in place, or a rebuild of the tables
     // the memory-bound outside-tile kernel and the VALU-bound inside-tile kernel are independent: the former runs on
@@ -154,8 +176,8 @@ private:
         GoesFirst,   // ApplyBatch: a recorded eye is launched before the size is looked at
         OnChange     // Apply: only where the plan changes, and a ctx-owned image it was handed in is retired, not freed
     };
-    int EnsurePlanned(const DeviceGuard &guard, const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout, Recorded recorded, hipStream_t stream);
-    bool PlannedFor(const ovrfsr_image &in, bool onlyOneEye, bool compareEyeLayout) const;
+    int EnsurePlanned(const DeviceGuard &guard, const Asked &asked, Recorded recorded, hipStream_t stream);
+    bool PlannedFor(const Asked &asked) const;
     hipStream_t Fork(hipStream_t user, bool overlap);
     void Join(hipStream_t user, hipStream_t aux);
 
@@ -181,16 +203,16 @@ private:
 
     int Fail(int status, const std::string &what);
     int CheckImage(const ovrfsr_image *img, const char *name, bool input = false); // input: may be multisampled / R11G11B10F
-    int PrepareResources(const ovrfsr_image &in, bool onlyOneEye, hipStream_t stream); // :498-561: plan (pipeline_plan.h), then upload
+    int PrepareResources(const Asked &asked, hipStream_t stream); // :498-561: plan (pipeline_plan.h), then upload
     // one masked launch round: images first, first + step, ... (cnt of them) of the batch, all of eye `eye` when `split`
     struct EyePass {
         int eye; uint32_t cnt, first, step; bool split;
         template <class Args> void Select(Args &a) const; // narrows an argument block of the whole batch (its view, its mask) to this pass
     };
-    int EyePasses(uint32_t n, int firstEye, int alternate, EyePass out[2]) const;
+    int EyePasses(const Call &call, EyePass out[2]) const;
     // body(const EyePass &, hipStream_t aux) -> hipError_t, once per pass, between Fork and Join; `what` names the launch in the error text.
     // `mayOverlap` = false: no fork -- aux is the caller's stream, and no event is recorded or waited on
-    template <class Body> int ForEachEyePass(uint32_t n, int firstEye, int alternate, hipStream_t stream, bool mayOverlap, const char *what, Body body);
+    template <class Body> int ForEachEyePass(const Call &call, bool mayOverlap, const char *what, Body body);
     // one pass's two launches: `inside` with the list of the tiles touching the radius (+ `ring` tiles behind them) on the caller's stream,
     // then `outside` with the list and records of the other tiles on the auxiliary one
     template <class In, class Out, class LaunchIn, class LaunchOut>
@@ -202,25 +224,28 @@ private:
     const uint32_t *SpanRecords(int eye) const { return spanRecDev_ + 2 * plan_.spanOff[eye]; }
     void RcasOverList(RcasArgs &a, int eye) const; // RCAS on the tiles the plan lists for it (Plan::nRcas), by span records where it has them
     int Launched(hipError_t e, const char *what); // OVRFSR_OK, or OVRFSR_ERR_HIP with "<what> launch: <hip error>"
-    template <class Args> void FillScale(Args &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
-    void FillRcas(RcasArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
-    void FillEasu(EasuArgs &a, const ovrfsr_image &in, size_t inStride, const ovrfsr_image &out, size_t outStride, int firstEye, int alternate) const;
-    void FillNis(NisArgs &a, int firstEye, int alternate) const;
+    template <class Args> void FillScale(Args &a, const ImageRun &in, const ImageRun &out, const Call &call) const;
+    void FillRcas(RcasArgs &a, const ImageRun &in, const ImageRun &out, const Call &call) const;
+    void FillEasu(EasuArgs &a, const ImageRun &in, const ImageRun &out, const Call &call) const;
+    void FillNis(NisArgs &a, const ImageRun &in, const ImageRun &out, const Call &call) const; // (the view and the tile grid too)
     int EnsureBuffer(DeviceBuffer &buf, size_t need);
-    int IntermediateImage(uint32_t n, ovrfsr_image *mid, size_t *midStride); // the upscale stage's destination in front of a sharpening stage
+    int IntermediateImage(uint32_t n, ImageRun *mid); // the upscale stage's destination in front of a sharpening stage
     int RefuseDisablingDestination(uint32_t format);
     float TieHalfMin() const;
-    int ApplyPostProcess(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                         const ovrfsr_image &out, size_t outStride, hipStream_t stream); // :563-638
-    int ApplyUpscaling(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                       const ovrfsr_image &out, size_t outStride, hipStream_t stream);   // :385-401
-    int ApplySorted(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                    const ovrfsr_image &out, size_t outStride, hipStream_t stream);
-    int ApplyFused(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                   const ovrfsr_image &out, size_t outStride, hipStream_t stream);
-    int ApplySharpening(uint32_t n, int firstEye, int alternate, const ovrfsr_image &in, size_t inStride,
-                        const ovrfsr_image &out, size_t outStride, hipStream_t stream);  // :483-496
-    void FillMask(MaskArgs &m, int firstEye, int alternate) const;
+    // one apply: `submitted` -> `out`, the FINAL destination (:563-638), and its steps in order --
+    int ApplyPostProcess(const Call &call, const ImageRun &submitted, const ImageRun &out);
+    // the pipeline's input: the submission itself, or the resolve / unpack pass into resolved_, or the BGRA8 re-order into swizzled_
+    // (starts the timer: in front of the resolve, behind the re-order)
+    int PipelineInput(const Call &call, const ImageRun &submitted, uint32_t outFormat, bool timing, ImageRun *in);
+    // the HDR wrap: the forward map of *in into hdrIn_, which takes its place, and the run in hdrOut_ in *out's (the back map follows the form)
+    int HdrWrap(const Call &call, ImageRun *in, ImageRun *out);
+    // the form switch; `mid`: the two-pass form's intermediate
+    int ApplyForm(const Call &call, const ImageRun &in, const ImageRun &mid, const ImageRun &out);
+    int ApplyUpscaling(const Call &call, const ImageRun &in, const ImageRun &out);  // :385-401
+    int ApplySorted(const Call &call, const ImageRun &in, const ImageRun &out);
+    int ApplyFused(const Call &call, const ImageRun &in, const ImageRun &out);
+    int ApplySharpening(const Call &call, const ImageRun &in, const ImageRun &out); // :483-496
+    void FillMask(MaskArgs &m, const Call &call) const;
 };
 
 } // namespace ovrfsr
