@@ -549,6 +549,63 @@ OVRFSR_API int ovrfsr_get_max_input_size(const ovrfsr_ctx *ctx, uint32_t *max_wi
  * maximum was set */
 OVRFSR_API int ovrfsr_rescale_stats(const ovrfsr_ctx *ctx, uint32_t *rescales, uint32_t *rebuilds);
 
+/* ---- mask feather: the edge of the radius mask, ramped over a band -----------------------------------------
+ * The radius mask's edge is a staircase of 16x16 groups: EASU + RCAS at full sharpness on one side of a group boundary, a plain bilinear
+ * sample on the other.  With a feather WIDTH set, one small pass runs behind the unchanged pipeline, over the band only, and blends every
+ * band pixel between what the pipeline stored there and the value that pixel has when its group is outside, by an integer weight that
+ * falls from 256 to 0 across the band.  No kernel of the pipeline changes, no plan, no tile list: the pass goes by the mask constants the
+ * launches in front of it carried.  No ABI version and no config field changes with these: a host probes for the symbols.
+ *
+ * width: in cfg.radius's unit (out_height / 2); 0 = off, the default; finite, 0 <= width <= 2.
+ *
+ * THE RULE.  For one apply, centre[4] and R = radius[0] are what ovrfsr_mask_constants gives that apply, a gaze included.
+ *     F   = f2u(0.5f * width * out_height)     the expression of radius[0], the same float -> uint rule
+ *     Ro  = R > 12 ? R - 12 : 0                outer edge of the ramp (12: the guard, below)
+ *     Ri  = Ro > F ? Ro - F : 0                inner edge
+ *     den = Ro * Ro - Ri * Ri                  64-bit
+ * The feather is ACTIVE for an eye iff F >= 1, Ro >= 1 and that eye's groups are mixed (some inside, some outside the radius).  For output
+ * pixel (x, y), in signed 64-bit integers with the centre words zero-extended:
+ *     d2 = min over the two centres k of (cx_k - x)^2 + (cy_k - y)^2
+ *     w8 = clamp(floor(256 * (Ro * Ro - d2) / den), 0, 256)
+ * A pixel is a BAND PIXEL iff its 16x16 group is inside by the reference's own rule (fsr_easu.hlsl:41-45, uint32 wrap-around and all,
+ * unchanged) and w8 < 256.  Pixels of outside groups are never touched.  A band pixel gets, per RGB channel, in fp32 with every operator
+ * rounded once and nothing fused,
+ *     t = w8 / 256.0f        v = o + (s - o) * t
+ * stored with the destination's store conversion; alpha keeps the stored value.
+ *   s  the destination's texel as the pipeline stored it, decoded: the byte the same call writes with the feather off.
+ *   o  the value that pixel has when its group is OUTSIDE, in the reference's operator order (the strict build's and the oracle's value),
+ *      decoded from the destination format: (1) the bilinear fallback sample (D3D rule, unfused); (2) where a sharpen stage follows, stored
+ *      to and reloaded from the intermediate format, then the RCAS outside branch's debug_mode tint; (3) stored to and reloaded from the
+ *      destination format.
+ * THE GUARD of 12 makes every pixel with w8 > 0 lie in an inside group: a pixel is at most sqrt(8^2 + 8^2) = 11.32 from its group's centre,
+ * a pixel with w8 > 0 has d < Ro = R - 12, so its group's centre is closer than R to the mask centre.  w8 is therefore 0 everywhere along
+ * the staircase: a band pixel there holds exactly o, and the step is gone.  The fully sharp region shrinks to d < Ri; a host compensates
+ * with cfg.radius (raise both together).
+ *
+ * WHERE IT APPLIES.  Every FSR form with an upscale stage (upscale-only, two-pass, mask-sorted, fused, fused with outside tiles), all three
+ * precisions (OVRFSR_PRECISION_FP32_EXACT keeps its promise: s is the strict byte, the blend is deterministic), batches, shared
+ * side-by-side textures, pair_submit, gaze and re-scale.  Under a hidden-area mesh the pixels of skipped tiles are neither read nor
+ * written.  Under OVRFSR_HDR_DOMAIN_SRTM the pass belongs to step 3 of that contract: it runs on the mapped RGBA32F copy and the RGBA32F
+ * result, in front of the back pass.  NIS (cfg.use_nis) and the sharpen-only forms IGNORE the setting: nothing is launched, their bytes
+ * are unchanged.  With the width 0, or an eye whose groups are not mixed, nothing is launched: plans, launches and bytes are what they
+ * are without these calls.
+ *
+ * LATCHING, like ovrfsr_set_gaze: the setter stores the value and nothing else -- no recorded pair_submit eye dropped, no rebuild, a
+ * disabled ctx stays disabled.  The apply that launches reads it; a recorded pair launches with the width in effect at its SECOND call.
+ * It is accepted under stream capture, and so is the apply behind it (the pass allocates and uploads nothing); a captured graph replays
+ * the width it was captured with.  ovrfsr_reset and ovrfsr_set_config keep the value.
+ *
+ * OVRFSR_ERR_INVALID_ARGUMENT -- the stored value left as it was -- for a NULL ctx or a width that is NaN, infinite, negative or above 2. */
+OVRFSR_API int ovrfsr_set_mask_feather(ovrfsr_ctx *ctx, float width);
+OVRFSR_API int ovrfsr_get_mask_feather(const ovrfsr_ctx *ctx, float *width);
+/* launches of the feather pass since the ctx was created (one per eye pass of an apply with an active eye) */
+OVRFSR_API int ovrfsr_mask_feather_stats(const ovrfsr_ctx *ctx, uint32_t *launches);
+/* Constants-only, no GPU: the rule above for a whole out_w x out_h image -- per pixel, row-major, w8 (0..256; 256 everywhere where F = 0 or
+ * Ro = 0) and whether its group is inside.  radius_px = radius[0], feather_px = F.  `len`: the element count of each array.
+ * OVRFSR_ERR_INVALID_ARGUMENT, nothing written, for a NULL pointer, a size of 0 or above 16384, or len < out_w * out_h. */
+OVRFSR_API int ovrfsr_mask_feather_weights(const uint32_t centre[4], uint32_t radius_px, uint32_t feather_px, uint32_t out_w, uint32_t out_h,
+                                           uint16_t *w8, uint8_t *inside, size_t len);
+
 /* ---- constants-only entry points (known-answer tests; no GPU needed) ------------------------- */
 
 /* FsrEasuCon (src/fsr/ffx_fsr1.h:156-202); con = con0|con1|con2|con3 */

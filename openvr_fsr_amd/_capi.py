@@ -134,6 +134,11 @@ def library():
         L.ovrfsr_set_max_input_size.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.ovrfsr_get_max_input_size.argtypes = [C.c_void_p, u32p, u32p]
         L.ovrfsr_rescale_stats.argtypes = [C.c_void_p, u32p, u32p]
+    if hasattr(L, "ovrfsr_set_mask_feather"):  # (probed the same way)
+        L.ovrfsr_set_mask_feather.argtypes = [C.c_void_p, C.c_float]
+        L.ovrfsr_get_mask_feather.argtypes = [C.c_void_p, f32p]
+        L.ovrfsr_mask_feather_stats.argtypes = [C.c_void_p, u32p]
+        L.ovrfsr_mask_feather_weights.argtypes = [u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_size_t]
     if L.ovrfsr_abi_version() != 5:
         raise OvrFsrError(1, "ABI version mismatch")
     _LIB = L
@@ -163,6 +168,17 @@ def mask_constants(outW, outH, proj, radius, only_one_eye, eye):
     library().ovrfsr_mask_constants(_u32p(centre), _u32p(rad), outW, outH, p.ctypes.data_as(C.POINTER(C.c_float)),
                                     radius, int(only_one_eye), int(eye))
     return centre, rad
+
+
+def mask_feather_weights(centre, radius_px, feather_px, outW, outH):
+    """ovrfsr_mask_feather_weights: ([outH, outW] uint16 w8, [outH, outW] uint8 group-inside flags) of the feather rule (no GPU)."""
+    c = np.ascontiguousarray(np.asarray(centre, np.uint32).reshape(4))
+    w8, inside = np.zeros((outH, outW), np.uint16), np.zeros((outH, outW), np.uint8)
+    rc = library().ovrfsr_mask_feather_weights(_u32p(c), int(radius_px), int(feather_px), int(outW), int(outH),
+                                               w8.ctypes.data_as(C.POINTER(C.c_uint16)), inside.ctypes.data_as(C.POINTER(C.c_uint8)), w8.size)
+    if rc != 0:
+        raise OvrFsrError(rc, "ovrfsr_mask_feather_weights")
+    return w8, inside
 
 
 def nis_scaler_config(sharpness, inW, inH, outW, outH):

@@ -10,6 +10,7 @@
 #include "fsr_launch.h"
 #include "fsr_bounds.h"
 #include "hdr_map.h"
+#include "mask_feather.h"
 #include "nis_tables.h"
 
 struct ovrfsr_ctx {
@@ -205,6 +206,47 @@ OVRFSR_API int ovrfsr_rescale_stats(const ovrfsr_ctx *ctx, uint32_t *rescales, u
 {
     if (!ctx || !rescales || !rebuilds) return OVRFSR_ERR_INVALID_ARGUMENT;
     ctx->pp->RescaleStats(rescales, rebuilds);
+    return OVRFSR_OK;
+}
+
+// ---- mask feather (header).  The argument checks live here; the setter stores and nothing else (PostProcessor::SetMaskFeather), so it needs
+// no guard: nothing in it allocates or throws.
+OVRFSR_API int ovrfsr_set_mask_feather(ovrfsr_ctx *ctx, float width)
+{
+    if (!ctx || !(width >= 0.0f && width <= 2.0f)) return OVRFSR_ERR_INVALID_ARGUMENT; // (NaN fails both comparisons; the stored value stays)
+    ctx->pp->SetMaskFeather(width);
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_get_mask_feather(const ovrfsr_ctx *ctx, float *width)
+{
+    if (!ctx || !width) return OVRFSR_ERR_INVALID_ARGUMENT;
+    *width = ctx->pp->MaskFeather();
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_mask_feather_stats(const ovrfsr_ctx *ctx, uint32_t *launches)
+{
+    if (!ctx || !launches) return OVRFSR_ERR_INVALID_ARGUMENT;
+    *launches = ctx->pp->MaskFeatherLaunches();
+    return OVRFSR_OK;
+}
+
+OVRFSR_API int ovrfsr_mask_feather_weights(const uint32_t centre[4], uint32_t radius_px, uint32_t feather_px, uint32_t out_w, uint32_t out_h,
+                                           uint16_t *w8, uint8_t *inside, size_t len)
+{
+    if (!centre || !w8 || !inside || out_w == 0 || out_h == 0 || out_w > 16384 || out_h > 16384 || len < (size_t)out_w * out_h)
+        return OVRFSR_ERR_INVALID_ARGUMENT; // (nothing written)
+    ovrfsr::FeatherCon fc;
+    const bool ramp = ovrfsr::feather_constants(radius_px, feather_px, &fc);
+    const uint32_t r2 = radius_px * radius_px; // radius[1], with its wrap-around
+    for (uint32_t y = 0; y < out_h; ++y)
+        for (uint32_t x = 0; x < out_w; ++x) {
+            const size_t i = (size_t)y * out_w + x;
+            // (no ramp -- F = 0 or Ro = 0 --: the feather is not active, every pixel keeps its value)
+            w8[i] = (uint16_t)(ramp ? ovrfsr::feather_w8(fc, ovrfsr::feather_d2(centre, x, y)) : 256u);
+            inside[i] = ovrfsr::feather_group_inside(centre, r2, x, y) ? 1 : 0;
+        }
     return OVRFSR_OK;
 }
 

@@ -512,6 +512,8 @@ hipError_t tie_audit_read_rcas(unsigned long long out[5], bool reset)
 #include "fsr_tile_records.inc"
 // ... and the tap tables of a rescale-capable ctx, refilled on the device when the input size moves (tap_tables_kernel)
 #include "fsr_tap_tables.inc"
+// ... and the pass of ovrfsr_set_mask_feather over the band of the radius mask's edge (mask_feather_kernel)
+#include "fsr_mask_feather.inc"
 namespace ovrfsr {
 
 hipError_t launch_easu(int prec, int in_fmt, int out_fmt, const EasuArgs &a_in, uint32_t batch, hipStream_t s, uint32_t nTiles)

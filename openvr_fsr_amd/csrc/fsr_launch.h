@@ -39,6 +39,8 @@ hipError_t launch_hdr_back(int fmt, const uint8_t *src, uint8_t *dst, uint32_t d
 hipError_t launch_tile_records(const TileRecordsArgs &a, hipStream_t s);
 // the column taps, their padding copies and the row taps for the two sizes of `a`, in place (fsr_tap_tables.inc)
 hipError_t launch_tap_tables(const TapTablesArgs &a, hipStream_t s);
+// the mask-feather pass over tilesW x tilesH tiles of `batch` images, in place on a.v.out (fsr_mask_feather.inc)
+hipError_t launch_mask_feather(const FeatherArgs &a, uint32_t tilesW, uint32_t tilesH, uint32_t batch, hipStream_t s);
 hipError_t launch_outside_staged(int tileH, int in_fmt, int mid_fmt, int out_fmt, const OutsideArgs &a, uint32_t nTiles, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_outside(int in_fmt, int out_fmt, const NisArgs &a, uint32_t nGroups, uint32_t batch, hipStream_t s);
 hipError_t launch_nis_sharpen(int prec, int in_fmt, int out_fmt, const NisArgs &a, uint32_t batch, hipStream_t s);

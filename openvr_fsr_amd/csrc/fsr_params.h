@@ -129,6 +129,22 @@ struct TapTablesArgs {
     uint32_t tapYOff;
 };
 
+// mask_feather_kernel (fsr_mask_feather.inc; the rule: mask_feather.h): the pass behind the pipeline over the band of the mask's edge.
+// v.in: the pipeline's input, v.out: the destination, read and written in place.  One workgroup per tile of the box
+// [tile0X, + gridDim.x) x [tile0Y, + gridDim.y) of the output's 32x32 tile grid.
+struct FeatherArgs {
+    BatchView v;
+    MaskArgs m;
+    const BilinTap *bilX;     // [outW], [outH]: the bilinear fallback's taps (EasuArgs)
+    const BilinTap *bilY;
+    const uint32_t *hiddenBits[2]; // per eye: bit t = tile t is skipped under the hidden-area mesh (neither read nor written); null: none is
+    uint32_t tilesX, tilesY;  // the output's tile grid (what hiddenBits indexes)
+    uint32_t tile0X, tile0Y;
+    uint32_t R, F;            // radius[0] and the feather width in pixels (feather_px)
+    int32_t inFmt, midFmt, outFmt; // FMT_*; midFmt < 0: no sharpen stage follows the upscale
+    uint32_t debug;           // RCAS const0[3]: the outside branch's tint
+};
+
 struct RcasArgs {
     BatchView v;
     float sharp;            // FsrRcasCon con[0] as float

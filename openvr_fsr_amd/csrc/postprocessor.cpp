@@ -10,6 +10,7 @@
 #include <vector>
 #include "fsr_formats.h"
 #include "fsr_launch.h"
+#include "mask_feather.h"
 
 namespace ovrfsr {
 
@@ -189,8 +190,9 @@ void PostProcessor::FreeTables()
     if (gazeStage_) (void)hipHostFree(gazeStage_);
     gazeStage_ = nullptr;
     hiddenMaps_ = HiddenMaps{};
-    for (void *t : {(void *)nisCoefDev_, (void *)bilinDev_, (void *)tileListDev_})
+    for (void *t : {(void *)nisCoefDev_, (void *)bilinDev_, (void *)tileListDev_, (void *)hiddenBitsDev_})
         if (t) (void)hipFree(t);
+    hiddenBitsDev_ = nullptr;
     nisCoefDev_ = nullptr;
     bilinDev_ = nullptr;
     tileListDev_ = tileRecDev_ = spanRecDev_ = nullptr;
@@ -558,8 +560,42 @@ int PostProcessor::PrepareResources(const Asked &asked, hipStream_t stream)
             if ((!q.start && event_create(&q.start, hipEventDefault) != hipSuccess) || (!q.end && event_create(&q.end, hipEventDefault) != hipSuccess))
                 return Fail(OVRFSR_ERR_HIP, "hipEventCreate failed");
     }
+    // (last, so that every creation in front of it keeps its place in the order fault injection counts by)
+    if (plan_.hiddenArea && (plan_.nSkipped[0] || plan_.nSkipped[1])) {
+        const int rc = BuildHiddenBits(hidden);
+        if (rc != OVRFSR_OK) return rc;
+    }
     initialized_ = true;
     return OVRFSR_OK;
+}
+
+// The skipped tiles of a plan under a hidden-area mesh as bits, per eye, for the mask-feather pass: from the maps the planner left (a gaze- or
+// rescale-capable plan), or rasterised here by the same rule (hidden_tiles) -- one eye per texture: each eye's own mesh; a shared
+// side-by-side texture: one map of both halves, the same for both eyes.
+int PostProcessor::BuildHiddenBits(const HiddenArea &mesh)
+{
+    const TileGrid &g = plan_.grid;
+    const size_t tiles = g.tiles(), words = (tiles + 31) / 32;
+    HiddenMaps local;
+    const HiddenMaps *maps = &hiddenMaps_;
+    if (hiddenMaps_.eye[0].size() != tiles || hiddenMaps_.eye[1].size() != tiles) {
+        for (int eye = 0; eye < 2; ++eye) local.eye[eye].assign(tiles, 0);
+        if (plan_.onlyOneEye) {
+            for (int eye = 0; eye < 2; ++eye)
+                hidden_tiles(mesh.uv[eye], mesh.triangles[eye], nullptr, 0, false, plan_.outputWidth, plan_.outputHeight, g.tileW, g.tileH, local.eye[eye].data());
+        } else {
+            hidden_tiles(mesh.uv[0], mesh.triangles[0], mesh.uv[1], mesh.triangles[1], true, plan_.outputWidth, plan_.outputHeight, g.tileW, g.tileH, local.eye[0].data());
+            local.eye[1] = local.eye[0];
+        }
+        maps = &local;
+    }
+    std::vector<uint32_t> bits(2 * words, 0u);
+    for (int eye = 0; eye < 2; ++eye)
+        for (size_t t = 0; t < tiles; ++t)
+            if (maps->eye[eye][t]) bits[eye * words + t / 32] |= 1u << (t & 31);
+    hipError_t e = dev_malloc(reinterpret_cast<void **>(&hiddenBitsDev_), bits.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(hiddenBitsDev_, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    return e == hipSuccess ? OVRFSR_OK : BuildFailed(e, "hidden-tile bitmap: ");
 }
 
 BatchView PostProcessor::make_view(const ImageRun &from, const ImageRun &to)
@@ -838,6 +874,49 @@ int PostProcessor::ApplySharpening(const Call &call, const ImageRun &in, const I
     return Launched(launch_rcas(plan_.rcasPrec, inFormat, outFormat, a, call.n, stream), "RCAS");
 }
 
+// The mask-feather pass (header, "Mask feather"; the rule: mask_feather.h), behind the form's last launch and the join of the auxiliary
+// stream, on the caller's stream, once per eye pass.  Everything it goes by is what the launches in front of it carried: the mask constants
+// of the moment (gaze included), the tap tables, the formats; the width is read here, by the apply that launches.  The grid is the box of
+// the disc(s) in tiles, computed per launch.  Nothing is allocated, nothing is uploaded.  Off, an eye that is not MASK_MIXED, NIS and the
+// forms without an upscale stage: no launch.
+int PostProcessor::ApplyFeather(const Call &call, const ImageRun &in, const ImageRun &out)
+{
+    if (!(feather_ > 0.0f) || plan_.useNis || !plan_.doUpscale) return OVRFSR_OK;
+    if (plan_.maskMode[0] != MASK_MIXED && plan_.maskMode[1] != MASK_MIXED) return OVRFSR_OK;
+    FeatherCon fc;
+    const uint32_t F = feather_px(feather_, plan_.outputHeight);
+    if (!feather_constants(plan_.radius[0], F, &fc)) return OVRFSR_OK;
+    FeatherArgs a;
+    a.v = make_view(in, out);
+    FillMask(a.m, call);
+    a.bilX = bilinDev_; a.bilY = bilinDev_ + plan_.tapYOff;
+    const size_t words = ((size_t)plan_.grid.tiles() + 31) / 32;
+    a.hiddenBits[0] = hiddenBitsDev_; a.hiddenBits[1] = hiddenBitsDev_ ? hiddenBitsDev_ + words : nullptr;
+    a.tilesX = plan_.grid.tx; a.tilesY = plan_.grid.ty;
+    a.tile0X = a.tile0Y = 0;
+    a.R = plan_.radius[0]; a.F = F;
+    a.inFmt = (int32_t)in.first.format; a.midFmt = plan_.doSharpen ? (int32_t)plan_.intermediateFormat : -1; a.outFmt = (int32_t)out.first.format;
+    a.debug = plan_.rcasCon[3];
+    return ForEachEyePass(call, false, "mask feather", [&](const EyePass &ps, hipStream_t) {
+        FeatherArgs b = a;
+        ps.Select(b);
+        // the box of the eyes this pass holds that are feathered
+        uint32_t box[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
+        for (uint32_t i = 0; i < 2 && i < ps.cnt; ++i) {
+            const uint32_t eye = (b.m.first_eye ^ (i & b.m.alternate)) & 1u;
+            uint32_t e[4];
+            if (plan_.maskMode[eye] != MASK_MIXED || !feather_box(plan_.centre[eye], a.R, plan_.outputWidth, plan_.outputHeight, e)) continue;
+            box[0] = std::min(box[0], e[0]); box[1] = std::min(box[1], e[1]); box[2] = std::max(box[2], e[2]); box[3] = std::max(box[3], e[3]);
+        }
+        if (box[0] >= box[2] || box[1] >= box[3]) return hipSuccess;
+        b.tile0X = box[0] / kTileW; b.tile0Y = box[1] / kTileH;
+        const uint32_t tw = (box[2] + kTileW - 1) / kTileW - b.tile0X, th = (box[3] + kTileH - 1) / kTileH - b.tile0Y;
+        const hipError_t e = launch_mask_feather(b, tw, th, ps.cnt, call.stream);
+        if (e == hipSuccess) ++featherLaunches_;
+        return e;
+    });
+}
+
 // The pipeline's input: the submission itself, or a ctx-owned copy of it in pipeline_format.  `timing`: the debug-mode timer starts here.
 int PostProcessor::PipelineInput(const Call &call, const ImageRun &submitted, uint32_t outFormat, bool timing, ImageRun *in)
 {
@@ -929,6 +1008,8 @@ int PostProcessor::ApplyPostProcess(const Call &call, const ImageRun &submitted,
     if (rc == OVRFSR_OK && plan_.form == Form::TwoPass) rc = IntermediateImage(call.n, &mid);
     if (rc != OVRFSR_OK) return rc; // (a step in front of the form's launches failed: the timer's end is not recorded)
     rc = ApplyForm(call, in, mid, pipeOut);
+    // (under the HDR domain the feather belongs to step 3 of that contract: on the mapped copy and the RGBA32F result, in front of the back pass)
+    if (rc == OVRFSR_OK) rc = ApplyFeather(call, in, pipeOut);
     if (hdr && rc == OVRFSR_OK)
         rc = Launched(launch_hdr_back((int)out.first.format, static_cast<const uint8_t *>(hdrOut_.p), static_cast<uint8_t *>(out.first.data), out.first.pitch_bytes,
                                       out.stride, out.first.width, out.first.height, call.n, call.stream), "HDR back map");

@@ -60,6 +60,11 @@ public:
     int SetMaxInputSize(uint32_t width, uint32_t height);
     void MaxInputSize(uint32_t *width, uint32_t *height) const { *width = maxInput_[0]; *height = maxInput_[1]; }
     void RescaleStats(uint32_t *rescales, uint32_t *rebuilds) const { *rescales = rescales_; *rebuilds = sizeRebuilds_; }
+    // ovrfsr_set_mask_feather / ovrfsr_get_mask_feather / ovrfsr_mask_feather_stats behind their argument checks.  The setter stores and
+    // nothing else, like SetGaze: the apply that launches reads the value (ApplyPostProcess -> ApplyFeather)
+    void SetMaskFeather(float width) { feather_ = width; }
+    float MaskFeather() const { return feather_; }
+    uint32_t MaskFeatherLaunches() const { return featherLaunches_; }
 #ifdef OVRFSR_BOUNDS
     int DebugReadTaps(void *dst, size_t bytes); // checked builds: the device tap tables as they are once the stream work so far is done
 #endif
@@ -100,6 +105,10 @@ private:
     // applies whose input size differed from the planned one and that re-scaled in place / rebuilt, since create
     uint32_t maxInput_[2] = {0, 0};
     uint32_t rescales_ = 0, sizeRebuilds_ = 0;
+    // ovrfsr_set_mask_feather's value (0: off), in cfg.radius's unit: outlives Reset and SetConfig like the four above, and touches no plan
+    // -- the pass behind the pipeline reads it with the mask constants of the moment.  featherLaunches_: launches of that pass since create
+    float feather_ = 0.0f;
+    uint32_t featherLaunches_ = 0;
 
     // PostProcessor.h:16-24
     bool enabled_ = true;
@@ -117,6 +126,10 @@ private:
     uint32_t *tileListDev_ = nullptr;     // Plan::lists, then inside the same allocation:
     uint32_t *tileRecDev_ = nullptr;      //   Plan::recs, 4 dwords per list entry
     uint32_t *spanRecDev_ = nullptr;      //   Plan::spans, 2 dwords per segment
+    // under a hidden-area mesh that skips a tile: per eye, one bit per tile of the grid (bit t of word t / 32: tile t is hidden), for the
+    // mask-feather pass, which neither reads nor writes such a tile.  The mesh decides it alone: a re-aim or a re-scale leaves it as it is
+    uint32_t *hiddenBitsDev_ = nullptr;   // eye 0's words, then eye 1's
+    int BuildHiddenBits(const HiddenArea &mesh);
     // A gaze-capable plan (Plan::gazeCapable): the same three tables laid out in the plan's per-eye regions, the records built on the device
     // (tile_records_kernel), and what a re-aim needs to put new lists there without a host wait: the hidden-area maps the planner rasterised,
     // and a ring of pinned staging slots, each a host image of the lists and spans (lists | spans, the device layout), each guarded by an
@@ -245,6 +258,8 @@ private:
     int ApplySorted(const Call &call, const ImageRun &in, const ImageRun &out);
     int ApplyFused(const Call &call, const ImageRun &in, const ImageRun &out);
     int ApplySharpening(const Call &call, const ImageRun &in, const ImageRun &out); // :483-496
+    // the mask-feather pass (header, "Mask feather") behind the form's launches: `in` the pipeline's input, `out` what the form wrote
+    int ApplyFeather(const Call &call, const ImageRun &in, const ImageRun &out);
     void FillMask(MaskArgs &m, const Call &call) const;
 };
 

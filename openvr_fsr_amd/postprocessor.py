@@ -181,6 +181,23 @@ class PostProcessor:
         self._check_arg(self._lib.ovrfsr_rescale_stats(self._ctx, C.byref(rescales), C.byref(rebuilds)), "ovrfsr_rescale_stats")
         return rescales.value, rebuilds.value
 
+    def set_mask_feather(self, width):
+        """ovrfsr_set_mask_feather: the width of the ramp at the radius mask's edge, in cfg.radius's unit; 0 (the default) is off.  Stored
+        only: the apply that launches reads it."""
+        self._check_arg(self._lib.ovrfsr_set_mask_feather(self._ctx, float(width)), "ovrfsr_set_mask_feather")
+
+    def mask_feather(self):
+        """ovrfsr_get_mask_feather"""
+        w = C.c_float()
+        self._check_arg(self._lib.ovrfsr_get_mask_feather(self._ctx, C.byref(w)), "ovrfsr_get_mask_feather")
+        return w.value
+
+    def mask_feather_stats(self):
+        """ovrfsr_mask_feather_stats: launches of the feather pass since the ctx was created."""
+        n = C.c_uint32()
+        self._check_arg(self._lib.ovrfsr_mask_feather_stats(self._ctx, C.byref(n)), "ovrfsr_mask_feather_stats")
+        return n.value
+
     def _check_arg(self, rc, what):
         if rc != 0:  # (an argument check of the C ABI: it leaves ovrfsr_last_error alone)
             raise K.OvrFsrError(rc, what)
